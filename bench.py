@@ -18,8 +18,13 @@ count-then-payload over RCCL (mhip_seed_reads_sharded / mhip_align_sharded), so 
 and overlap set.
 
 Prints ONE JSON line on rank 0 (see the task contract): value = candidate overlaps/sec of the whole job, plus
-aligned Gbase/sec, a `roofline` block for the dominant kernel and a `cpu_baseline` block (the unmodified reference
-mecat2pw from oracle/_ref, or the oracle port, timed on this host on a bounded sample).
+aligned Gbase/sec and a `roofline` block for the dominant kernel.  A plain run does only that: set up, warm up, time the
+--steps steps, print the line.  `--full` adds everything else the line has carried: the `cpu_baseline` block (the unmodified
+reference mecat2pw from oracle/_ref, or the oracle port, timed on this host on a bounded sample), the end-to-end CLI leg, the
+untimed extra stages and workloads, and the live issue-rate calibration of the dw roofline.
+
+`--dump-outputs DIR` writes what the last timed step computed as float64 .npy files (write_outputs): the candidate count of every
+read, and the candidate lists and extension results of a fixed, seeded sample of reads.
 """
 import argparse
 import ctypes as C
@@ -38,10 +43,39 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_READS, DUMP_SEED = 2048, 1234      # --dump-outputs: size and seed of the read sample whose lists and results are written
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_sample(n):
+    """the reads whose candidate lists and extension results --dump-outputs writes: the same sorted sample in every run"""
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_READS), replace=False))
+
+
+def dump_rows(counts, sample, maxc):
+    """[S, maxc] rows of a read-major result table (read r's results are rows first[r] .. first[r] + counts[r] - 1, the job order of
+    mhip_jobs_from_candidates_dev and mhip_align_sharded) that hold the sampled reads' results; row 0 in the empty slots"""
+    first = np.cumsum(counts, dtype=np.int64) - counts
+    slot = np.arange(maxc)
+    return np.where(slot[None, :] < counts[sample][:, None], first[sample][:, None] + slot[None, :], 0)
+
+
+def write_outputs(d, counts, sample, cands, res):
+    """--dump-outputs: what the timed path hands its caller, as float64 (every value is an int32, so exact).
+    counts int32[n]: candidates of every read; cands int32[S, maxc, 12]: the candidate lists (CAND_DTYPE fields) of the reads in
+    `sample`; res int32[S, maxc, 8] or None (--no-align): the extension results (ALN_DTYPE fields) of those reads' jobs, in list order.
+    Slots past a read's count are written as zeros.  About 34 MB at config 2."""
+    os.makedirs(d, exist_ok=True)
+    live = np.arange(cands.shape[1])[None, :] < counts[sample][:, None]
+    out = {"sample_reads": sample, "candidate_counts": counts, "candidates": np.where(live[:, :, None], cands, 0)}
+    if res is not None:
+        out["extension_results"] = np.where(live[:, :, None], res, 0)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+    log("[bench] outputs of the last timed step -> %s: %s" % (d, ", ".join("%s %s" % (k, v.shape) for k, v in out.items())))
 
 
 def cpu_baseline(workload, nthreads):
@@ -374,6 +408,11 @@ def main():
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="config2")
+    ap.add_argument("--full", action="store_true", help="also everything beside the headline line: CPU baselines, the end-to-end CLI leg, the untimed "
+                                                       "extra stages and workloads, live issue-rate calibration (the --no-* flags below thin it out)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last one computed to DIR/<name>.npy "
+                                                                       "(float64): candidate counts of every read, candidate lists and extension "
+                                                                       "results of a fixed sample of %d reads" % DUMP_READS)
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--cpu-full", type=int, default=1, help="1 (default): also time the unmodified reference -j 0 on the full workload on this host, once")
     ap.add_argument("--no-align", action="store_true", help="-j 0 only (index + candidates)")
@@ -385,18 +424,25 @@ def main():
     ap.add_argument("--simulate-ranks", default="", help="e.g. 2,4,8: on ONE GPU, run every rank's share of the sharded calls alone (no transport) and report "
                                                          "per-rank times, imbalance, link bytes and the compute-only speed-up bound (prints its own JSON line)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:       # a plain run: only what the headline line needs
+        args.no_cpu = args.no_e2e = args.no_extras = True
 
     # `python bench.py --gpus N` without a launcher around it (no WORLD_SIZE in the environment): start N ranks of this script, one per
-    # GPU, through torch.distributed.run on the loop-back address, and become that launcher (the run must not
-    # quietly fall back to one GPU).  Under a launcher (WORLD_SIZE set) the ranks must be exactly --gpus.
+    # GPU, through torch.distributed.run on the loop-back address, as a child process (the run must not quietly
+    # fall back to one GPU).  Under a launcher (WORLD_SIZE set) the ranks must be exactly --gpus.
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         port = os.environ.get("MASTER_PORT", str(29500 + os.getpid() % 2000))
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
                "--master-port", port, os.path.abspath(__file__)] + sys.argv[1:]
-        log("[bench] --gpus %d without a launcher: exec %s" % (args.gpus, " ".join(cmd)))
-        os.execv(sys.executable, cmd)
+        log("[bench] --gpus %d without a launcher: running %s" % (args.gpus, " ".join(cmd)))
+        sys.exit(subprocess.run(cmd).returncode)
 
     from mecat_amd import workload as W
+    if args.dump_outputs and (args.workload == "config4" or args.workload in W.GRIDS):
+        raise SystemExit("bench.py: --dump-outputs is implemented for the single-volume workloads (%s)" % ", ".join(
+            k for k in W.CONFIGS if k not in {g[0] for g in W.GRIDS.values()}))
     if args.workload == "config4":      # BASELINE configs[3]: mecat2cns' re-alignment + accept stage on config 2's candidates (bench_config4.py)
         import bench_config4
         bench_config4.run(args)
@@ -561,6 +607,16 @@ def main():
             ok = r[:, 0] != 0
             aln_ok = int(ok.sum().item())
             aligned_bases = int(((r[:, 2] - r[:, 1]).to(torch.int64) * ok).sum().item())
+        if args.dump_outputs:
+            # only the sampled reads' rows leave the device
+            h_cnt = d_counts.cpu().numpy()
+            sample = dump_sample(n)
+            h_cands = d_cands.index_select(0, torch.from_numpy(sample).to(dev)).cpu().numpy()
+            h_res = None
+            if not args.no_align:
+                rows = dump_rows(h_cnt, sample, maxc)
+                h_res = d_res.index_select(0, torch.from_numpy(rows.ravel()).to(dev)).cpu().numpy().reshape(len(sample), maxc, 8)
+            write_outputs(args.dump_outputs, h_cnt, sample, h_cands, h_res)
     else:
         tr, nr = comm.info()
         exch = {"bytes_received_per_step": (comm.bytes_received() - index_how.get("bytes_received_measuring", 0)) / max(1, args.steps + args.warmup),
@@ -571,9 +627,10 @@ def main():
                 "index_build_kernels_ms": sum(v[1] for k, v in kstats.items() if k.startswith(("ix_", "idx"))) / args.steps,
                 "index_rebase_slots_ms": sum(v[1] for k, v in kstats.items() if k.startswith("xg_index")) / args.steps}
         idx = comm.index_build_auto(vol)[0]
-        _, h_cnt = comm.seed_reads_sharded(idx, vol, vol, 0, n, params, chunk=CH, cell_shift=0, host=True)
+        h_cands, h_cnt = comm.seed_reads_sharded(idx, vol, vol, 0, n, params, chunk=CH, cell_shift=0, host=True)
         ncand = int(h_cnt.sum())
         aln_ok = aligned_bases = 0
+        h_res = None
         if not args.no_align:
             h_res, nj = comm.align_sharded(vol, vol, params.min_align_size, tech=ont, host=True)
             assert nj == ncand
@@ -581,6 +638,12 @@ def main():
             aln_ok = int(okm.sum())
             aligned_bases = int((h_res["query_end"].astype(np.int64) - h_res["query_start"])[okm].sum())
         idx.free()
+        if args.dump_outputs and rank == 0:     # the complete tables, in the layout of the one-GPU run (results read-major)
+            sample = dump_sample(n)
+            res_s = None
+            if h_res is not None and len(h_res):
+                res_s = h_res.view(np.int32).reshape(-1, 8)[dump_rows(h_cnt, sample, maxc)]
+            write_outputs(args.dump_outputs, h_cnt, sample, h_cands.view(np.int32).reshape(n, maxc, 12)[sample], res_s)
         exch["records_per_step"] = ncand
         exch["index_build"] = index_how          # how the cell's table is built, and the two measured times the choice rests on
         # every rank's own phase times (HIP events on its stream, mean over the timed steps) and wall time: where a short curve fell short
@@ -652,7 +715,7 @@ def main():
         # instruction-issue rates of this device, calibrated live by mecat_amd/bin/valu_peak.  CDNA4 issues a wave64 VALU
         # instruction in 2 cycles only for the simple 32-bit class (add/sub/logic/mov/lshr, two waves of a SIMD co-issuing);
         # min/max, shifts left, compares, selects, every VOP3 / DPP / SGPR-operand form take 4.
-        if pk == "dw" and world == 1:
+        if pk == "dw" and world == 1 and args.full:      # (valu_peak is a run of its own: --full only)
             ceil = issue_ceilings()
             vi = {"unit": "G wave-instr/s", "ceilings": ceil}
             if pmc_ok and args.workload == "config2" and avg_ms > 0 and "error" not in ceil:

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 import helpers as H
@@ -19,19 +20,30 @@ def _line(out):
     return json.loads(lines[-1])
 
 
-def test_bench_line_one_rank_and_two_ranks_agree():
+def test_bench_line_one_rank_and_two_ranks_agree(tmp_path):
     bench = os.path.join(H.ROOT, "bench.py")
-    r1 = subprocess.run([sys.executable, bench, "--gpus", "1"] + FLAGS, capture_output=True, text=True, timeout=600)
+    r1 = subprocess.run([sys.executable, bench, "--gpus", "1", "--dump-outputs", str(tmp_path / "one")] + FLAGS, capture_output=True, text=True,
+                        timeout=600)
     assert r1.returncode == 0, r1.stderr[-2000:]
     a = _line(r1.stdout)
     assert a["n_gpus"] == 1 and a["value"] > 0 and a["roofline"]["achieved"] > 0
     env = dict(os.environ, MECAT_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     r2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                         "--master-port", "29541", bench, "--gpus", "2"] + FLAGS, capture_output=True, text=True, timeout=900, env=env)
+                         "--master-port", "29541", bench, "--gpus", "2", "--dump-outputs", str(tmp_path / "two")] + FLAGS, capture_output=True,
+                        text=True, timeout=900, env=env)
     assert r2.returncode == 0, r2.stderr[-3000:]
     b = _line(r2.stdout)
     assert b["n_gpus"] == 2 and b["scaling"] == "strong"
     assert b["candidates"] == a["candidates"] and b["overlaps_ok"] == a["overlaps_ok"]
+    # --dump-outputs: the same arrays from both runs, and they agree with the line
+    names = ["sample_reads", "candidate_counts", "candidates", "extension_results"]
+    assert sorted(os.listdir(tmp_path / "one")) == sorted(os.listdir(tmp_path / "two")) == sorted(k + ".npy" for k in names)
+    d1 = {k: np.load(tmp_path / "one" / (k + ".npy")) for k in names}
+    d2 = {k: np.load(tmp_path / "two" / (k + ".npy")) for k in names}
+    assert all(d1[k].dtype == np.float64 and np.array_equal(d1[k], d2[k]) for k in names)
+    assert d1["candidate_counts"].sum() == a["candidates"] and d1["candidates"].shape == (len(d1["sample_reads"]), 100, 12)
+    live = np.arange(100)[None, :] < d1["candidate_counts"][d1["sample_reads"].astype(np.int64)][:, None]
+    assert live.any() and (d1["extension_results"][..., 0][live] != 0).any() and not d1["extension_results"][~live].any()
     # the line says what the communicator was and what the exchanges cost (the first run on a node must show rccl / N ranks here)
     x = b["exchange"]
     assert x["transport"].startswith("host files") and x["rccl_ranks"] == 0 and x["ms"] > 0 and x["calls_per_step"] >= 2

@@ -17,11 +17,11 @@ python profiles/summarize_sq.py $TAG 2 $O/sq1 $O/sq2 $O/sq3 $O/sq4 > /dev/null
 rm -f /tmp/align_$TAG.s; python profiles/finish.py $TAG > /dev/null
 cp $P/* profiles/
 for f in kernel_stats.csv hbm_counters.md hbm_traffic.json instruction_mix.md instruction_mix.json pmc_source.json agent_info.csv; do cp profiles/${TAG}_$f $P/ 2>/dev/null; done
-(timeout 900 python bench.py > $F/config2.json 2> $F/config2.err)
-(timeout 600 python bench.py --workload config3 --steps 2 --warmup 1 > $F/config3.json 2> $F/config3.err)
-(timeout 600 python bench.py --workload config5_cell --steps 2 --warmup 1 > $F/config5_cell.json 2> $F/config5_cell.err)
-(timeout 900 python bench.py --workload config4 > $F/config4.json 2> $F/config4.err)
-if [ -n "$WITH_CONFIG5" ]; then (timeout 2200 python bench.py --workload config5 --steps 1 --warmup 0 > $F/config5.json 2> $F/config5.err); fi
+(timeout 900 python bench.py --full > $F/config2.json 2> $F/config2.err)
+(timeout 600 python bench.py --full --workload config3 --steps 2 --warmup 1 > $F/config3.json 2> $F/config3.err)
+(timeout 600 python bench.py --full --workload config5_cell --steps 2 --warmup 1 > $F/config5_cell.json 2> $F/config5_cell.err)
+(timeout 900 python bench.py --full --workload config4 > $F/config4.json 2> $F/config4.err)
+if [ -n "$WITH_CONFIG5" ]; then (timeout 2200 python bench.py --full --workload config5 --steps 1 --warmup 0 > $F/config5.json 2> $F/config5.err); fi
 wc -c $F/*.json
 if [ -n "$WITH_SWEEPS" ]; then      # the randomised parity sweeps against the oracle (profiles/rNN_parity_sweeps.md quotes their last lines)
   (SEED=4501 N=60 timeout 1500 python tools/dev/parity_sweep.py > gpurun_out/sweep_candidates_$TAG.log 2>&1; tail -2 gpurun_out/sweep_candidates_$TAG.log)
