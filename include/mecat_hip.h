@@ -283,7 +283,7 @@ int  mhip_asm_seed_reads_ex(mhip_ctx* ctx, const mhip_index* idx, const mhip_vol
  *   right  rx = x0,      ry = c.loc2,      rnx = c.right1, rny = c.right2    (forwards from its first base)
  * dirs[2 i + d] = {columns, x bases, y bases, y-only columns, x-only columns, 0} of direction d (0 left, 1 right);
  * ops[(2 i + d) * dir_cols_cap / 16 ...] the columns, 2 bits each, in extension order: 0 = both bases (always equal: O(ND) paths have
- * no mismatch columns), 1 = y base only, 2 = x base only. */
+ * no mismatch columns), 1 = y base only, 2 = x base only.  The bits behind a direction's last column are zero. */
 typedef struct { int32_t xid, yid, chain, lx, ly, lnx, lny, rx, ry, rnx, rny, pad; } mhip_asm_job;
 int  mhip_asm_extend(mhip_ctx* ctx, const mhip_volume* block, const mhip_volume* reads, const mhip_asm_job* jobs, int n, int dir_cols_cap,
                      int32_t* dirs /*[2 n][6]*/, uint32_t* ops /*[2 n][dir_cols_cap / 16]*/);

@@ -297,6 +297,68 @@ def asm_seed_reads(ctx, idx, block, reads, rid_begin, rid_end):
     return out, cnt
 
 
+ASM_JOB_DTYPE = np.dtype([(n, np.int32) for n in ("xid", "yid", "chain", "lx", "ly", "lnx", "lny", "rx", "ry", "rnx", "rny", "pad")])
+assert ASM_JOB_DTYPE.itemsize == 48
+
+
+def volume_set_nplane(ctx, vol, nplane):
+    """mhip_volume_set_nplane: the second 2-bit plane of a volume (non-zero at every base that is not A, C, G, T); None removes it"""
+    if nplane is not None:
+        nplane = np.ascontiguousarray(nplane, dtype=np.uint8)
+        assert len(nplane) >= (vol.num_bases + 3) // 4
+    _chk(lib().mhip_volume_set_nplane(ctx.h, vol.h, nplane.ctypes.data if nplane is not None else None))
+
+
+def asm_jobs_from_candidates(cands, counts, rid_begin=0):
+    """the (candidate, both directions) jobs of an asm_seed_reads table, read by read in list order (include/mecat_hip.h: x0 = loc1 - 1 -
+    readstart; left from (x0 + 12, loc2 + 12) with left1 / left2 bases, right from (x0, loc2) with right1 / right2) -> [n] ASM_JOB_DTYPE"""
+    counts = np.asarray(counts)
+    mask = np.arange(cands.shape[1])[None, :] < counts[:, None]
+    c = cands[mask]
+    jobs = np.zeros(len(c), dtype=ASM_JOB_DTYPE)
+    x0 = c["loc1"] - 1 - c["readstart"]
+    jobs["xid"], jobs["chain"] = c["readno"], c["chain"]
+    jobs["yid"] = rid_begin + np.repeat(np.arange(len(counts), dtype=np.int32), counts)
+    jobs["lx"], jobs["ly"], jobs["lnx"], jobs["lny"] = x0 + 12, c["loc2"] + 12, c["left1"], c["left2"]
+    jobs["rx"], jobs["ry"], jobs["rnx"], jobs["rny"] = x0, c["loc2"], c["right1"], c["right2"]
+    return jobs
+
+
+def asm_extend(ctx, block, reads, jobs, dir_cols_cap):
+    """mhip_asm_extend: the extension loop of mecat2asmpw / mecat2trimpw, fixed-stride form
+    -> (dirs int32[2 n, 6] = {cols, x bases, y bases, y-only, x-only, 0}, ops uint32[2 n, dir_cols_cap // 16])"""
+    jobs = np.ascontiguousarray(jobs, dtype=ASM_JOB_DTYPE)
+    n = len(jobs)
+    dirs = np.zeros((2 * n, 6), dtype=np.int32)
+    ops = np.zeros((2 * n, max(dir_cols_cap, 0) // 16), dtype=np.uint32)
+    L = lib()
+    L.mhip_asm_extend.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    _chk(L.mhip_asm_extend(ctx.h, block.h, reads.h, jobs.ctypes.data, n, dir_cols_cap, dirs.ctypes.data, ops.ctypes.data))
+    return dirs, ops
+
+
+def asm_extend_run(ctx, block, reads, jobs, dir_cols_cap):
+    """mhip_asm_extend_run: extends the batch, leaves the results on the device -> the 32-bit words of all directions' columns"""
+    jobs = np.ascontiguousarray(jobs, dtype=ASM_JOB_DTYPE)
+    total = C.c_int64()
+    L = lib()
+    L.mhip_asm_extend_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+    _chk(L.mhip_asm_extend_run(ctx.h, block.h, reads.h, jobs.ctypes.data, len(jobs), dir_cols_cap, C.byref(total)))
+    return int(total.value)
+
+
+def asm_extend_fetch(ctx, n, total_words):
+    """mhip_asm_extend_fetch for the last asm_extend_run on the context (n = its jobs, total_words = what it returned)
+    -> (dirs int32[2 n, 6], word_offs uint64[2 n + 1], ops_dense uint32[total_words])"""
+    dirs = np.zeros((2 * n, 6), dtype=np.int32)
+    offs = np.zeros(2 * n + 1, dtype=np.uint64)
+    dense = np.zeros(max(total_words, 1), dtype=np.uint32)
+    L = lib()
+    L.mhip_asm_extend_fetch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    _chk(L.mhip_asm_extend_fetch(ctx.h, n, dirs.ctypes.data, offs.ctypes.data, dense.ctypes.data))
+    return dirs, offs, dense[:total_words]
+
+
 def seed_reads(ctx, idx, ref, reads, rid_begin, rid_end, params):
     """-> (cands structured array [n, maxc], counts int32[n]) on the host"""
     n = rid_end - rid_begin

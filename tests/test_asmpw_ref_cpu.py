@@ -184,3 +184,39 @@ def test_candidate_stage_equals_reference(start, fresh):
     O.asm_block_free(B)
     assert total > 2000      # (7 000+ candidates with block 1 indexed, 2 400+ with block 2)
     assert reordered <= 3    # (reads whose list order differs between the reference's thread history and a fresh start: 0 and 1 on these sets)
+
+
+# ---- the extension loop of pairwise_mapping (mecat2asmpw.c:723-841): tests/golden/asm_ext.npz, what tests/test_gpu_asm_extend.py holds the device to
+def test_extension_fixture_is_consistent():
+    import numpy as np
+    g = np.load(os.path.join(H.GOLDEN, "asm_ext.npz"))
+    meta = json.loads(g["meta"].tobytes().decode())
+    jobs, dirs, sha = g["jobs"], g["dirs"], g["sha256"]
+    assert len(dirs) == 2 * len(jobs) == len(sha) >= 3000 and meta["ranges"]["long"][1] == len(jobs)
+    assert (dirs[:, 0] == dirs[:, 1] + dirs[:, 3]).all() and (dirs[:, 0] == dirs[:, 2] + dirs[:, 4]).all()
+    # what the generator promises and the file itself can show: both strands, empty directions, one of more than 40 000 columns, the
+    # word-boundary cases of the packing
+    assert set(jobs[:, 2].tolist()) == {0, 1}
+    assert (dirs[:, 0] == 0).sum() >= 20 and (dirs[:, 0] > 40000).sum() >= 1
+    assert {0, 1, 15} <= set((dirs[:, 0] % 16).tolist())
+    # no direction takes more bases than its candidate offers
+    avail = jobs[:, [5, 6, 9, 10]].reshape(-1, 2)
+    assert (dirs[:, 1] <= avail[:, 0]).all() and (dirs[:, 2] <= avail[:, 1]).all()
+    offs, words = g["full_offs"], g["full_words"]
+    assert len(g["full_dirs"]) > len(dirs) // 4
+    for i, k in enumerate(g["full_dirs"]):
+        w = words[offs[i]: offs[i + 1]]
+        assert len(w) == (dirs[k, 0] + 15) // 16 and hashlib.sha256(w.astype("<u4").tobytes()).digest() == sha[k].tobytes()
+        ops = ((w[:, None] >> (2 * np.arange(16, dtype=np.uint32))[None, :]) & 3).reshape(-1)
+        assert (ops[: dirs[k, 0]] == 1).sum() == dirs[k, 3] and (ops[: dirs[k, 0]] == 2).sum() == dirs[k, 4] and not ops[dirs[k, 0]:].any()
+
+
+@pytest.mark.skipif(not os.path.exists(os.path.join(H.ROOT, "oracle", "_ref", "libref_asmpw_ext.so")), reason="the reference harness is built in the build container only")
+def test_reference_reproduces_the_extension_fixture(tmp_path):
+    """the generator — the unmodified pairwise_mapping behind oracle/ref_harness_asmpw_ext.c, its coverage assertions included — writes
+    the committed file again, byte for byte"""
+    sys.path.insert(0, H.GOLDEN)
+    import make_golden_asm_ext as G
+    out = str(tmp_path / "asm_ext.npz")
+    G.main(out)
+    assert open(out, "rb").read() == open(os.path.join(H.GOLDEN, "asm_ext.npz"), "rb").read()

@@ -193,6 +193,29 @@ def test_drop_in_tool_equals_the_reference_run_on_this_machine(tmp_path, tool, s
     print("%s -S%d: %d lines, reference %.1f s on 32 threads, device tool %.1f s" % (tool, start, len(want), ref_s, dev_s))
 
 
+@pytest.mark.parametrize("tool,start,err,least", [("mecat2asmpw", 1, 0.05, 20000), ("mecat2trimpw", 2, 0.05, 6000),
+                                                  ("mecat2asmpw", 1, 0.10, 12000), ("mecat2trimpw", 2, 0.10, 4000)])
+def test_drop_in_tool_equals_the_reference_run_at_higher_error(tmp_path, tool, start, err, least):
+    """The same comparison on reads at 5 % and at 10 % error (10 % / 20 % between two reads) instead of 2 %.  `align`'s limit counts O(ND)
+    differences over both blocks and hardly binds at 5 %: of the 666 directions of the 5 % set of tests/golden/asm_ext.npz 4 are empty
+    and none ends with a block that failed.  At 10 % it does: of that set's 460 directions 150 are empty and 246 end early, with more
+    than 120 bases left on both sides — first blocks that fail, blocks dropped by the `loc == DN` rule — which is where the host's
+    string_check restatement and coordinate rules meet short and empty directions.  1 000 reads in two blocks, the UNMODIFIED tool and
+    the drop-in side by side on this machine: sorted outputs equal line by line (`least`: a round number under what the reference
+    prints for the set, 26 498 / 8 902 / 16 951 / 5 560 lines)."""
+    from mecat_amd import workload as W
+    ref = os.path.join(H.ROOT, "oracle", "_ref", tool)
+    if not os.path.exists(ref):
+        pytest.skip("oracle/_ref/%s is not built (make -C oracle ref, in the container)" % tool)
+    d = str(tmp_path)
+    W.asm_blocks_layout(d, 1000, 8000, 250_000, 2, 81, err=err)
+    want, _, _ = W.asm_tool_run(ref, d, 16, start, 2)
+    got, _, _ = W.asm_tool_run(os.path.join(H.ROOT, "mecat_amd", "bin", tool), d, 16, start, 2)
+    assert len(want) > least
+    bad = [(a, b) for a, b in zip(got, want) if a != b]
+    assert len(got) == len(want) and not bad, (len(got), len(want), bad[:3])
+
+
 @pytest.mark.parametrize("tool,start", [("mecat2asmpw", 1), ("mecat2trimpw", 1), ("mecat2asmpw", 2)])
 def test_reads_with_n_equal_the_reference_run_on_this_machine(tmp_path, tool, start):
     """Bases other than A, C, G, T: the tools restart their k-mer at such a base in table and query and compare it as a character in the
