@@ -362,6 +362,36 @@ void mhip_cns_free(void* p);
 /* test hook: normalize_gaps' gap pushing (reads_correction_aux.cpp:36-67) by the device kernel of the accept stage, in place, on n_pairs
  * pairs of NUL-terminated host strings: pair p = buf + off[p] (len[p] characters + NUL) and its partner right behind it */
 int  mhip_debug_push_gaps(mhip_ctx* ctx, char* buf, int64_t bytes, const int64_t* off, const int32_t* len, int n_pairs);
+/* ---- mecat2cns' consensus table, built in the accept stage (cns_table.hip).  The first thing the reference does with the strings of
+ * an accepted alignment is to fold them into the template's table of CnsTableItem {base, mat_cnt, ins_cnt, del_cnt}
+ * (reads_correction_aux.h:11-19): meap_add_one_aln, mecat_correction.cpp:36-60, called at :439 / :502; it then classifies every
+ * position (identify_one_consensus_item, :14-24: FMAT 1, FDEL 2, FINS 4, UNDS 8) and only positions flagged UNDS or FDEL look at the
+ * strings again (meap_consensus_one_segment, :81-108).  mhip_cns_accept_templates_ex is mhip_cns_accept_templates (same arguments
+ * without host_pac, same accepted records and strings) with `want` choosing the outputs:
+ *   MHIP_CNS_WANT_STRINGS   the aligned strings, as before
+ *   MHIP_CNS_WANT_TABLE     the tables and ident bytes of all templates: template t owns out_table[out_table_begin[t] ..
+ *                           out_table_begin[t + 1]), one item per base of the template read (whole read: positions no alignment
+ *                           covers hold {'N', 0, 0, 0} and ident 7, as in the reference's cleared table), no items for a template
+ *                           without candidates; out_ident is indexed alike; out_table_begin has num_templates + 1 entries.  `base` is
+ *                           the template's own letter where mat_cnt > 0 — what every match column writes there — else 'N'.
+ * With MHIP_CNS_WANT_TABLE alone the strings are built on the device (the tally reads them) but never copied: *out_strings is NULL,
+ * *out_strings_bytes 0 and str_offset -1 in every accepted record.  want == 0 is an error.  Outputs that were not asked for come back
+ * NULL (their pointers may be NULL then); all are released with mhip_cns_free.  Counts are bytes: at most 60 / 100 alignments are
+ * accepted per template, so none overflows.  Effective ranges, segment cutting and the POA refinement stay with the caller. */
+typedef struct { uint8_t base, mat_cnt, ins_cnt, del_cnt; } mhip_cns_table_item;   /* CnsTableItem */
+#define MHIP_CNS_WANT_STRINGS 1
+#define MHIP_CNS_WANT_TABLE   2     /* table + ident */
+int  mhip_cns_accept_templates_ex(mhip_ctx* ctx, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin,
+                                  int num_templates, int tech, int min_align_size, double min_mapping_ratio, int num_threads, int want,
+                                  mhip_cns_accepted** out_accepted, int64_t* out_count, char** out_strings, int64_t* out_strings_bytes,
+                                  int64_t* out_jobs, mhip_cns_table_item** out_table, uint8_t** out_ident,
+                                  int64_t** out_table_begin /* [num_templates + 1] */);
+/* test hook: the accept stage's two table kernels (tally, then base + ident) over n_pairs pairs of host strings in
+ * mhip_debug_push_gaps' layout, all alignments to one template: pair p starts at template position soff[p]; the base letters come from
+ * tmpl_letters[tmpl_len].  Refused before anything runs: more than 255 pairs, a mismatch column, a pair whose template span leaves
+ * [0, tmpl_len).  -> table_out[tmpl_len], ident_out[tmpl_len] */
+int  mhip_debug_cns_table(mhip_ctx* ctx, const char* buf, int64_t bytes, const int64_t* off, const int32_t* len, const int32_t* soff,
+                          int n_pairs, const char* tmpl_letters, int tmpl_len, mhip_cns_table_item* table_out, uint8_t* ident_out);
 /* mhip_cns_free does not return a string buffer to the system at once: the library keeps the LARGEST released one (gigabytes — about
  * 14 GB for a config-2-sized batch) and hands it out again to the next batch that fits, because first-touching fresh pages costs
  * more than the batch's GPU time.  The parked buffer belongs to the process, not to a context (mhip_ctx_destroy leaves it).  This call

@@ -14,6 +14,9 @@
 // re-aligned speculatively on the device (mhip_cns_align_candidates_dev, a slice of the batch's templates per launch), the sequential
 // accept decisions are replayed over the results on host threads, and the gap-normalised strings of the ACCEPTED alignments are
 // built on the device as well (cns_strings.hip) and copied into the result buffer while the next slice re-aligns.
+// mhip_cns_accept_templates_ex adds what the reference does with those strings first: the consensus table of every template
+// (meap_add_one_aln, :36-60, at :439 / :502) and its per-position classification (identify_one_consensus_item, :14-24), tallied
+// from the strings while they are still in device memory (cns_table.hip) — and, asked for the table alone, never copies the strings.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -31,6 +34,7 @@
 
 #include "common.h"
 #include "cns_strings.h"
+#include "cns_table.h"
 
 namespace {
 
@@ -80,6 +84,20 @@ void strbuf_free(void* p) {               // (g_strbuf_mu held or not: only the 
     if (reg) (void)hipHostUnregister(p);
     free(p);
 }
+// cap bytes (a multiple of 2 MB), touched and page-locked; registered buffers are noted in g_strbuf_reg
+void* locked_alloc(size_t cap, int num_threads) {
+    void* p = nullptr;
+    const size_t two_mb = (size_t)2 << 20;
+    if (posix_memalign(&p, two_mb, cap) != 0) return nullptr;
+    (void)madvise(p, cap, MADV_HUGEPAGE);
+    // first touch on the host threads (huge pages: 8 GB in 30 ms on 32 threads), then page-locked — 70 ms for 8 GB of touched pages, against
+    // 0.4 s untouched and 1.9 s for a hipHostMalloc of the size (tools/dev/probes/pin_probe.hip)
+    parallel_for((int64_t)(cap / two_mb), num_threads, [&](int64_t pg) { ((volatile char*)p)[(size_t)pg * two_mb] = 0; });
+    const bool reg = hipHostRegister(p, cap, hipHostRegisterDefault) == hipSuccess;
+    if (!reg) (void)hipGetLastError();      // stays pageable: the copies still work, through the runtime's staging
+    if (reg) { std::lock_guard<std::mutex> lk(g_strbuf_mu); g_strbuf_reg.insert(p); }
+    return p;
+}
 char* strbuf_get(size_t bytes, int num_threads) {
     {
         std::lock_guard<std::mutex> lk(g_strbuf_mu);
@@ -91,19 +109,19 @@ char* strbuf_get(size_t bytes, int num_threads) {
             return p;
         }
     }
-    void* p = nullptr;
     const size_t two_mb = (size_t)2 << 20, cap = (bytes + bytes / 16 + two_mb - 1) & ~(two_mb - 1);
-    if (posix_memalign(&p, two_mb, cap) != 0) return nullptr;
-    (void)madvise(p, cap, MADV_HUGEPAGE);
-    // first touch on the host threads (huge pages: 8 GB in 30 ms on 32 threads), then page-locked — 70 ms for 8 GB of touched pages, against
-    // 0.4 s untouched and 1.9 s for a hipHostMalloc of the size (tools/dev/probes/pin_probe.hip)
-    parallel_for((int64_t)(cap / two_mb), num_threads, [&](int64_t pg) { ((volatile char*)p)[(size_t)pg * two_mb] = 0; });
-    const bool reg = hipHostRegister(p, cap, hipHostRegisterDefault) == hipSuccess;
-    if (!reg) (void)hipGetLastError();      // stays pageable: the copies still work, through the runtime's staging
+    void* p = locked_alloc(cap, num_threads);
+    if (!p) return nullptr;
     std::lock_guard<std::mutex> lk(g_strbuf_mu);
     g_strbuf_out[p] = cap;
-    if (reg) g_strbuf_reg.insert(p);
     return (char*)p;
+}
+// a result buffer that the copy engine fills (the tables of a batch: 5 bytes per template base): page-locked from 64 MB on, plain
+// malloc below; never parked — mhip_cns_free unregisters and frees it
+void* result_alloc(size_t bytes, int num_threads) {
+    if (bytes < ((size_t)64 << 20)) return malloc(std::max<size_t>(bytes, 1));
+    const size_t two_mb = (size_t)2 << 20;
+    return locked_alloc((bytes + two_mb - 1) & ~(two_mb - 1), num_threads);
 }
 }  // namespace
 
@@ -138,10 +156,11 @@ void mhip_cns_release_parked(void) {
     strbuf_free(p);
 }
 
-int mhip_cns_accept_templates(mhip_ctx* c, const mhip_volume* vol, const uint8_t* /*host_pac: not read any more (the strings are built on the device)*/, mhip_ext_candidate* cands, const int64_t* tmpl_begin,
-                              int num_templates, int tech, int min_align_size, double min_mapping_ratio, int num_threads,
-                              mhip_cns_accepted** out_accepted, int64_t* out_count, char** out_strings, int64_t* out_strings_bytes,
-                              int64_t* out_jobs) {
+// the body of both entry points; want_tab: the outputs behind out_jobs are filled as well
+static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin,
+                           int num_templates, int tech, int min_align_size, double min_mapping_ratio, int num_threads, const bool want_str, const bool want_tab,
+                           mhip_cns_accepted** out_accepted, int64_t* out_count, char** out_strings, int64_t* out_strings_bytes,
+                           int64_t* out_jobs, mhip_cns_table_item** out_table, uint8_t** out_ident, int64_t** out_table_begin) {
     HIPCHK(hipSetDevice(c->device));
     *out_accepted = nullptr; *out_count = 0; *out_strings = nullptr; *out_strings_bytes = 0;
     if (out_jobs) *out_jobs = 0;
@@ -182,13 +201,40 @@ int mhip_cns_accept_templates(mhip_ctx* c, const mhip_volume* vol, const uint8_t
     if (bad.load() == 2) { mhip_set_error("cns accept: a candidate's qsize / ssize differs from the read lengths of the volume"); return -1; }
     if (bad.load()) { mhip_set_error("cns accept: a candidate is outside the volume, has sdir != 0 or sits in another template's range"); return -1; }
 
+    // the tables: one word per base of every template that has candidates, template after template
+    std::vector<int64_t> TB;
+    if (want_tab) {
+        TB.assign((size_t)num_templates + 1, 0);
+        for (int t = 0; t < num_templates; ++t)
+            TB[(size_t)t + 1] = TB[(size_t)t] + (tmpl_begin[t + 1] > tmpl_begin[t] ? (int64_t)vol->h_offs[(size_t)(cands[tmpl_begin[t]].sid - start_id)].size : 0);
+    }
+    const int64_t TW = want_tab ? TB[(size_t)num_templates] : 0;
+    // host buffers of the table outputs (filled by the copy stream), and the host arrays behind the slices' item copies: a set's arrays
+    // live until the copies that follow the kernels which read them have completed (declared in front of `cleanup`, which waits for them)
+    struct TabOut {
+        uint32_t* tab = nullptr; uint8_t* id = nullptr; int64_t* begin = nullptr;
+        ~TabOut() { mhip_cns_free(tab); mhip_cns_free(id); free(begin); }
+    } tab_out;
+    std::vector<CnsStrItem> hold_items[2];
+    std::vector<CnsTabItem> hold_titems[2];
+    std::vector<long long> hold_first[2];
+    std::vector<int32_t> hold_voloff[2];
+    auto hand_over_tables = [&]() -> int {          // (after the last copy has landed)
+        tab_out.begin = (int64_t*)malloc(sizeof(int64_t) * ((size_t)num_templates + 1));
+        if (!tab_out.begin) { mhip_set_error("out of memory"); return -1; }
+        memcpy(tab_out.begin, TB.data(), sizeof(int64_t) * ((size_t)num_templates + 1));
+        *out_table = (mhip_cns_table_item*)tab_out.tab; *out_ident = tab_out.id; *out_table_begin = tab_out.begin;
+        tab_out.tab = nullptr; tab_out.id = nullptr; tab_out.begin = nullptr;
+        return 0;
+    };
+
     lap(0);
     // 2. the first <= 200 candidates of every template, as alignment jobs
     std::vector<int64_t> jfirst((size_t)num_templates + 1, 0);
     for (int t = 0; t < num_templates; ++t) jfirst[(size_t)t + 1] = jfirst[(size_t)t] + std::min<int64_t>(max_ext, tmpl_begin[t + 1] - tmpl_begin[t]);
     const int64_t nj = jfirst[(size_t)num_templates];
     if (out_jobs) *out_jobs = nj;
-    if (nj == 0) return 0;
+    if (nj == 0) return want_tab ? hand_over_tables() : 0;
     if (nj > 0x7fffffffLL) { mhip_set_error("cns accept: too many jobs in one batch"); return -1; }
     std::vector<mhip_aln_job> jobs((size_t)nj);
     parallel_for(num_templates, num_threads, [&](int64_t t) {
@@ -282,6 +328,11 @@ int mhip_cns_accept_templates(mhip_ctx* c, const mhip_volume* vol, const uint8_t
         S = nS; S_cap = want; S_big = big;
         return 0;
     };
+    if (TW > 0) {
+        tab_out.tab = (uint32_t*)result_alloc(sizeof(uint32_t) * (size_t)TW, num_threads);
+        tab_out.id = (uint8_t*)result_alloc((size_t)TW, num_threads);
+        if (!tab_out.tab || !tab_out.id) { mhip_set_error("out of memory (%lld table positions)", (long long)TW); return -1; }
+    }
     double est_scale = 1.15;
     if (const char* e = getenv("MECAT_CNS_STR_ESTIMATE")) est_scale = std::max(0.01, atof(e) / 100.0);
 
@@ -349,14 +400,19 @@ int mhip_cns_accept_templates(mhip_ctx* c, const mhip_volume* vol, const uint8_t
             }
         sl.sbytes = off;
     };
-    // strings of an (aligned, replayed) slice: built on the device behind whatever the stream holds, copied on the second stream
+    // strings of an (aligned, replayed) slice: built on the device behind whatever the stream holds, copied on the second stream; the
+    // slice's tables (whole templates: a contiguous piece of the output) zeroed, tallied from the strings and finished behind them
     auto strings_slice = [&](Slice& sl, int b, int k) -> int {
         const int64_t na = (int64_t)sl.items.size();
-        if (na == 0) return 0;
-        size_t want = S_used + sl.sbytes;
-        if (want > S_cap && k + 1 < nslices)
-            want = std::max(want, (size_t)((double)want / (double)sl.t1 * (double)num_templates * est_scale) + ((size_t)1 << 20));
-        if (s_reserve(want)) return -1;
+        const int64_t tw0 = want_tab ? TB[(size_t)sl.t0] : 0, tw = want_tab ? TB[(size_t)sl.t1] - tw0 : 0;
+        if (na == 0 && tw == 0) return 0;
+        if (want_str && na) {
+            size_t want = S_used + sl.sbytes;
+            if (want > S_cap && k + 1 < nslices)
+                want = std::max(want, (size_t)((double)want / (double)sl.t1 * (double)num_templates * est_scale) + ((size_t)1 << 20));
+            if (s_reserve(want)) return -1;
+        }
+        std::vector<CnsTabItem> titems((size_t)(want_tab ? na : 0));
         // the accepted records (what the caller gets beside the strings)
         const size_t a0 = Avec.size();
         Avec.resize(a0 + (size_t)na);
@@ -373,21 +429,63 @@ int mhip_cns_accept_templates(mhip_ctx* c, const mhip_volume* vol, const uint8_t
                 o.qid = ec.qid; o.sid = ec.sid;
                 o.qoff = r.qoff; o.qend = r.qend; o.soff = r.soff; o.send = r.send;
                 o.aln_size = it.aln_size;
-                o.str_offset = (int64_t)(S_used + it.off);
+                o.str_offset = want_str ? (int64_t)(S_used + it.off) : -1;
+                if (want_tab) {
+                    CnsTabItem& ti = titems[(size_t)(sl.afirst[(size_t)tl] + (int64_t)kk)];
+                    ti.off = it.off; ti.tab = (unsigned long long)(TB[(size_t)t] - tw0); ti.aln_size = it.aln_size; ti.soff = r.soff;
+                    ti.tab_len = (int32_t)(TB[(size_t)t + 1] - TB[(size_t)t]); ti.pad = 0;
+                }
             }
         });
-        if (k >= 2) HIPCHK(hipEventSynchronize(ev_copied[b]));      // the copy out of this set's string buffer two slices ago (the buffer may move)
-        char* d_str;
-        CnsStrItem* d_items;
-        if (c->scratch(b ? "ca_str1" : "ca_str", sl.sbytes + 128, (void**)&d_str)) return -1;
-        if (c->scratch(b ? "ca_items1" : "ca_items", sizeof(CnsStrItem) * (size_t)na, (void**)&d_items)) return -1;
-        HIPCHK(hipMemcpyAsync(d_items, sl.items.data(), sizeof(CnsStrItem) * (size_t)na, hipMemcpyHostToDevice, c->stream));
-        if (cns_strings_launch(c, vol, d_jobs + sl.j0, d_res[b], d_ops[b], row_words, d_items, (int)na, d_str)) return -1;
+        if (k >= 2) HIPCHK(hipEventSynchronize(ev_copied[b]));      // the copies out of this set's buffers two slices ago (the string buffer may move)
+        // (that slice's host arrays are done with now: this slice's take their place)
+        hold_items[b].swap(sl.items);
+        hold_titems[b].swap(titems);
+        char* d_str = nullptr;
+        if (na) {
+            CnsStrItem* d_items;
+            if (c->scratch(b ? "ca_str1" : "ca_str", sl.sbytes + 128, (void**)&d_str)) return -1;
+            if (c->scratch(b ? "ca_items1" : "ca_items", sizeof(CnsStrItem) * (size_t)na, (void**)&d_items)) return -1;
+            HIPCHK(hipMemcpyAsync(d_items, hold_items[b].data(), sizeof(CnsStrItem) * (size_t)na, hipMemcpyHostToDevice, c->stream));
+            if (cns_strings_launch(c, vol, d_jobs + sl.j0, d_res[b], d_ops[b], row_words, d_items, (int)na, d_str)) return -1;
+        }
+        uint32_t* d_tab = nullptr;
+        uint8_t* d_id = nullptr;
+        if (tw) {
+            std::vector<long long>& first = hold_first[b];
+            std::vector<int32_t>& voloff = hold_voloff[b];
+            first.clear(); voloff.clear();
+            for (int t = sl.t0; t < sl.t1; ++t)
+                if (TB[(size_t)t + 1] > TB[(size_t)t]) {
+                    first.push_back((long long)(TB[(size_t)t] - tw0));
+                    voloff.push_back(vol->h_offs[(size_t)(cands[tmpl_begin[t]].sid - start_id)].offset);
+                }
+            const int ntm = (int)voloff.size();
+            first.push_back((long long)tw);
+            CnsTabItem* d_titems;
+            long long* d_first;
+            int32_t* d_voloff;
+            if (c->scratch(b ? "ca_tab1" : "ca_tab", sizeof(uint32_t) * (size_t)tw, (void**)&d_tab)) return -1;
+            if (c->scratch(b ? "ca_ident1" : "ca_ident", (size_t)tw, (void**)&d_id)) return -1;
+            if (c->scratch(b ? "ca_titems1" : "ca_titems", sizeof(CnsTabItem) * (size_t)std::max<int64_t>(na, 1), (void**)&d_titems)) return -1;
+            if (c->scratch(b ? "ca_tfirst1" : "ca_tfirst", sizeof(long long) * ((size_t)ntm + 1), (void**)&d_first)) return -1;
+            if (c->scratch(b ? "ca_tvoloff1" : "ca_tvoloff", sizeof(int32_t) * (size_t)ntm, (void**)&d_voloff)) return -1;
+            if (na) HIPCHK(hipMemcpyAsync(d_titems, hold_titems[b].data(), sizeof(CnsTabItem) * (size_t)na, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(d_first, first.data(), sizeof(long long) * ((size_t)ntm + 1), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(d_voloff, voloff.data(), sizeof(int32_t) * (size_t)ntm, hipMemcpyHostToDevice, c->stream));
+            if (cns_table_launch(c, vol, d_str, d_titems, (int)na, d_tab, d_id, (long long)tw, d_first, d_voloff, ntm, nullptr)) return -1;
+        }
         HIPCHK(hipEventRecord(ev_built[b], c->stream));
         HIPCHK(hipStreamWaitEvent(copy_stream, ev_built[b], 0));
-        HIPCHK(hipMemcpyAsync(S + S_used, d_str, sl.sbytes, hipMemcpyDeviceToHost, copy_stream));
+        if (want_str && na) {
+            HIPCHK(hipMemcpyAsync(S + S_used, d_str, sl.sbytes, hipMemcpyDeviceToHost, copy_stream));
+            S_used += sl.sbytes;
+        }
+        if (tw) {
+            HIPCHK(hipMemcpyAsync(tab_out.tab + tw0, d_tab, sizeof(uint32_t) * (size_t)tw, hipMemcpyDeviceToHost, copy_stream));
+            HIPCHK(hipMemcpyAsync(tab_out.id + tw0, d_id, (size_t)tw, hipMemcpyDeviceToHost, copy_stream));
+        }
         HIPCHK(hipEventRecord(ev_copied[b], copy_stream));
-        S_used += sl.sbytes;
         return 0;
     };
 
@@ -415,10 +513,11 @@ int mhip_cns_accept_templates(mhip_ctx* c, const mhip_volume* vol, const uint8_t
     }
     HIPCHK(hipStreamSynchronize(copy_stream));
     const int64_t na = (int64_t)Avec.size();
-    if (na == 0) return 0;
+    if (na == 0) return want_tab ? hand_over_tables() : 0;
     mhip_cns_accepted* A = (mhip_cns_accepted*)malloc(sizeof(mhip_cns_accepted) * (size_t)na);
     if (!A) { mhip_set_error("out of memory"); return -1; }
     memcpy(A, Avec.data(), sizeof(mhip_cns_accepted) * (size_t)na);
+    if (want_tab && hand_over_tables()) { free(A); return -1; }
     const int64_t sbytes = (int64_t)S_used;
     s_guard.armed = false;
     lap(5);
@@ -431,6 +530,28 @@ int mhip_cns_accept_templates(mhip_ctx* c, const mhip_volume* vol, const uint8_t
     *out_strings = S;
     *out_strings_bytes = sbytes;
     return 0;
+}
+
+int mhip_cns_accept_templates(mhip_ctx* c, const mhip_volume* vol, const uint8_t* /*host_pac: not read any more (the strings are built on the device)*/, mhip_ext_candidate* cands, const int64_t* tmpl_begin,
+                              int num_templates, int tech, int min_align_size, double min_mapping_ratio, int num_threads,
+                              mhip_cns_accepted** out_accepted, int64_t* out_count, char** out_strings, int64_t* out_strings_bytes,
+                              int64_t* out_jobs) {
+    return cns_accept_body(c, vol, cands, tmpl_begin, num_templates, tech, min_align_size, min_mapping_ratio, num_threads, true, false, out_accepted, out_count,
+                           out_strings, out_strings_bytes, out_jobs, nullptr, nullptr, nullptr);
+}
+
+int mhip_cns_accept_templates_ex(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin, int num_templates, int tech,
+                                 int min_align_size, double min_mapping_ratio, int num_threads, int want, mhip_cns_accepted** out_accepted, int64_t* out_count,
+                                 char** out_strings, int64_t* out_strings_bytes, int64_t* out_jobs, mhip_cns_table_item** out_table, uint8_t** out_ident,
+                                 int64_t** out_table_begin) {
+    const bool want_tab = (want & MHIP_CNS_WANT_TABLE) != 0;
+    if (want == 0 || (want & ~(MHIP_CNS_WANT_STRINGS | MHIP_CNS_WANT_TABLE))) { mhip_set_error("cns accept: want = %d (MHIP_CNS_WANT_STRINGS | MHIP_CNS_WANT_TABLE)", want); return -1; }
+    if (want_tab && (!out_table || !out_ident || !out_table_begin)) { mhip_set_error("cns accept: the table was asked for without a place to put it"); return -1; }
+    if (out_table) *out_table = nullptr;
+    if (out_ident) *out_ident = nullptr;
+    if (out_table_begin) *out_table_begin = nullptr;
+    return cns_accept_body(c, vol, cands, tmpl_begin, num_templates, tech, min_align_size, min_mapping_ratio, num_threads, (want & MHIP_CNS_WANT_STRINGS) != 0, want_tab,
+                           out_accepted, out_count, out_strings, out_strings_bytes, out_jobs, out_table, out_ident, out_table_begin);
 }
 
 }  // extern "C"

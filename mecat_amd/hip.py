@@ -122,6 +122,9 @@ def lib():
     L.mhip_sharded_tables.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
     L.mhip_cns_accept_templates.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, C.c_double, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp),
                                             C.POINTER(i64), C.POINTER(i64)]
+    L.mhip_cns_accept_templates_ex.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_double, i32, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp),
+                                               C.POINTER(i64), C.POINTER(i64), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.mhip_debug_cns_table.argtypes = [vp, vp, i64, vp, vp, vp, i32, vp, i32, vp, vp]
     L.mhip_cns_free.argtypes = [vp]
     L.mhip_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
     L.mhip_host_free.argtypes = [vp]
@@ -459,6 +462,63 @@ def cns_accept_templates(ctx, vol, host_pac, cands, tmpl_begin, tech, min_align_
     s = np.ctypeslib.as_array(C.cast(st, C.POINTER(C.c_uint8)), shape=(sb.value,))
     weakref.finalize(s, lib().mhip_cns_free, C.c_void_p(st.value))
     return a, s, nj.value
+
+
+CNS_WANT_STRINGS, CNS_WANT_TABLE = 1, 2
+TABLE_DTYPE = np.dtype([("base", np.uint8), ("mat_cnt", np.uint8), ("ins_cnt", np.uint8), ("del_cnt", np.uint8)])      # CnsTableItem
+IDENT_FMAT, IDENT_FDEL, IDENT_FINS, IDENT_UNDS = 1, 2, 4, 8
+
+
+def _cns_buffer(ptr, nbytes):
+    """uint8 array over a buffer of the library (no copy), released with mhip_cns_free when the array goes"""
+    import weakref
+    if not ptr.value or not nbytes:
+        lib().mhip_cns_free(ptr)
+        return np.zeros(0, np.uint8)
+    a = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(nbytes,))
+    weakref.finalize(a, lib().mhip_cns_free, C.c_void_p(ptr.value))
+    return a
+
+
+def cns_accept_templates_ex(ctx, vol, cands, tmpl_begin, tech, min_align_size, min_mapping_ratio, want, threads=8):
+    """cns_accept_templates with the outputs chosen by `want` (CNS_WANT_STRINGS | CNS_WANT_TABLE): the consensus tables of the templates
+    (meap_add_one_aln) and their ident bytes (identify_one_consensus_item) come from the device.
+    -> (accepted, strings, number of alignments computed, table [TABLE_DTYPE], ident [uint8], table_begin [templates + 1]): template t
+    owns table[table_begin[t]: table_begin[t + 1]], one item per base of the read.  Without CNS_WANT_STRINGS `strings` is empty and every
+    str_offset -1; without CNS_WANT_TABLE the last three are empty."""
+    cands = np.ascontiguousarray(cands)
+    tb = np.ascontiguousarray(tmpl_begin, dtype=np.int64)
+    acc, st, tab, idn, tbeg = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    na, sb, nj = C.c_int64(), C.c_int64(), C.c_int64()
+    _chk(lib().mhip_cns_accept_templates_ex(ctx.h, vol.h, cands.ctypes.data, tb.ctypes.data, len(tb) - 1, tech, min_align_size, float(min_mapping_ratio), threads,
+                                            int(want), C.byref(acc), C.byref(na), C.byref(st), C.byref(sb), C.byref(nj), C.byref(tab), C.byref(idn), C.byref(tbeg)))
+    a = np.ctypeslib.as_array(C.cast(acc, C.POINTER(C.c_uint8)), shape=(na.value * 48,)).view(ACCEPTED_DTYPE).copy() if na.value else np.zeros(0, ACCEPTED_DTYPE)
+    lib().mhip_cns_free(acc)
+    s = _cns_buffer(st, sb.value)
+    if tbeg.value:
+        begin = np.ctypeslib.as_array(C.cast(tbeg, C.POINTER(C.c_int64)), shape=(len(tb),)).copy()
+        lib().mhip_cns_free(tbeg)
+    else:
+        begin = np.zeros(0, np.int64)
+    nw = int(begin[-1]) if len(begin) else 0
+    return a, s, nj.value, _cns_buffer(tab, 4 * nw).view(TABLE_DTYPE), _cns_buffer(idn, nw), begin
+
+
+def debug_cns_table(ctx, buf, off, lens, soff, tmpl_letters):
+    """test hook: the accept stage's table kernels over pairs of aligned strings to one template.  buf: uint8 buffer, pair p = q at
+    off[p] (lens[p] characters + NUL), s right behind it; soff[p] = template position of its first template base; tmpl_letters: bytes.
+    -> (table [len(tmpl_letters)] TABLE_DTYPE, ident uint8)"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    soff = np.ascontiguousarray(soff, dtype=np.int32)
+    let = np.frombuffer(bytes(tmpl_letters), dtype=np.uint8)
+    assert len(off) == len(lens) == len(soff)
+    table = np.zeros(len(let), TABLE_DTYPE)
+    ident = np.zeros(len(let), np.uint8)
+    _chk(lib().mhip_debug_cns_table(ctx.h, buf.ctypes.data, len(buf), off.ctypes.data, lens.ctypes.data, soff.ctypes.data, len(off), let.ctypes.data, len(let),
+                                    table.ctypes.data, ident.ctypes.data))
+    return table, ident
 
 
 COMM_ID_BYTES = 128
