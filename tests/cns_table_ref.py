@@ -1,6 +1,7 @@
 """A plain numpy statement of mecat2cns' consensus table rules, for the tests of the device table (mecat_amd/csrc/cns_table.hip).
 
-Written from the rules, not from the reference's loop; test_cns_table_ref_cpu.py pins it against hand-computed tables.
+Written from the rules, not from the reference's loop; test_cns_table_ref_cpu.py pins it against hand-computed tables and against what the
+compiled, unmodified reference gives (tests/golden/cns_table.npz: meap_add_one_aln on adversarial pairs, every ident byte).
 
 One alignment is two equally long strings over "ACGT-" (q: the query read, s: the template) and `soff`, the template position of the
 first template base.  The template position of column i is
@@ -78,3 +79,17 @@ def build_table(alns, tmpl_letters):
     table["mat_cnt"], table["ins_cnt"], table["del_cnt"] = counts[:, 0], counts[:, 1], counts[:, 2]
     table["base"] = np.where(counts[:, 0] > 0, let, ord("N"))
     return table, ident_of(counts[:, 0], counts[:, 1], counts[:, 2])
+
+
+MAX_CNS_OVLPS = 100      # the most alignments mecat2cns gives one template: the largest coverage a table position can have
+
+
+def sweep_triples(max_cov=MAX_CNS_OVLPS):
+    """every (mat, ins, del) a position of the table can hold with mat + ins <= max_cov and del <= mat + ins, in the order of
+    tests/golden/cns_table.npz `sweep_ident`: cov = mat + ins ascending, then mat ascending, then del ascending  -> int32 [348 551, 3]"""
+    rows = []
+    for cov in range(max_cov + 1):
+        mat = np.repeat(np.arange(cov + 1), cov + 1)
+        dele = np.tile(np.arange(cov + 1), cov + 1)
+        rows.append(np.stack([mat, cov - mat, dele], axis=1))
+    return np.concatenate(rows).astype(np.int32)

@@ -313,6 +313,31 @@ def ref_cns():
     return _ref_cns
 
 
+_ref_cns_table = None
+
+
+def ref_cns_table_available():
+    return os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libref_cns_table.so"))
+
+
+def ref_cns_table():
+    """harness that exposes the unmodified mecat2cns' consensus table (oracle/ref_harness_cns_table.cpp)"""
+    global _ref_cns_table
+    if _ref_cns_table is None:
+        L = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libref_cns_table.so"))
+        vp = C.c_void_p
+        L.refc_load_reads.argtypes = [C.c_char_p]
+        L.refc_consensus_can_table.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, C.c_long, C.POINTER(C.c_long), vp, C.c_int,
+                                               C.POINTER(C.c_int)]
+        L.refc_add_one_aln.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, vp]
+        L.refc_identify.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.refc_identify_table.argtypes = [vp, C.c_int, vp]
+        L.refc_identify_triples.argtypes = [vp, C.c_long, vp]
+        assert L.refc_item_size() == 4
+        _ref_cns_table = L
+    return _ref_cns_table
+
+
 def cns_pair(rng, n, err, it):
     """two noisy copies of a random sequence and a seed point near their shared diagonal (code arrays, int8)"""
     g = rng.integers(0, 4, size=n + 1200).astype(np.int8)

@@ -2,19 +2,27 @@
 mhip_debug_cns_table): what meap_add_one_aln (mecat_correction.cpp:36-60) folds the accepted strings into, and the ident byte
 identify_one_consensus_item (:14-24) gives every position.
 
-How it is pinned.  No harness under oracle/ exposes the reference's table, so the table is pinned to the reference THROUGH THE
-REFERENCE'S STRINGS PLUS A RESTATEMENT OF A 20-LINE LOOP: the pipeline test first shows that the accepted alignments and their strings
-are the unmodified reference's (tests/golden/cns_accept.npz: coordinates and SHA-256 per template, as test_gpu_cns_accept.py), then that
-table and ident equal tests/cns_table_ref.py applied to those strings, byte for byte.  That restatement is itself pinned to
-hand-computed tables (test_cns_table_ref_cpu.py), and one property is checked without it: mat_cnt + ins_cnt at a position is the number
-of accepted alignments covering it, from the golden coordinates alone.  The kernels' own corner cases (64-column steps, runs across
-steps, byte carries) go through the test hook."""
+How it is pinned.  TO THE COMPILED, UNMODIFIED REFERENCE, as every other device stage of the mecat2cns path:
+oracle/_ref/libref_cns_table.so (oracle/ref_harness_cns_table.cpp holds mecat_correction.cpp itself) exposes the table a template is left
+with, meap_add_one_aln and identify_one_consensus_item, and tests/golden/cns_table.npz (make_golden_cns_table.py) records what they give:
+  * the table and ident bytes of all 240 + 160 templates of the golden accept sets, as a SHA-256 per template and in full for the first 8
+    of each set: the pipeline (CNS_WANT_TABLE alone) must give those bytes
+  * the ident byte of every count triple a position can hold (mat + ins <= 100, del <= mat + ins): one hook call builds exactly those
+    counts on a template of 348 551 letters
+  * meap_add_one_aln on 1 060 adversarial pairs (the reference's own normalize_gaps outputs of pushgaps.npz, and generated pairs with long
+    template-gap runs: beginning with double gaps, double gaps only, at the first and last column, at soff == 0), guards included
+  * a volume whose first read id is not 0 must give the bytes of the same reads numbered from 0.
+tests/cns_table_ref.py, the restatement of the rules, is held against the same recorded results on the CPU (test_cns_table_ref_cpu.py)
+and stays the checker of the kernels' own corner cases through the test hook (64-column steps, runs across steps, byte carries) and of
+the subset test below, which also shows that the strings are the reference's and checks one property without any restatement:
+mat_cnt + ins_cnt at a position is the number of accepted alignments covering it, from the golden coordinates alone."""
 import hashlib
 import os
 
 import numpy as np
 import pytest
 
+import cns_table_golden as TG
 import cns_table_ref as R
 import helpers as H
 
@@ -156,26 +164,26 @@ SUBSET = {"pacbio": 48, "nanopore": 32}
 _volumes = {}
 
 
-def golden_subset(name):
+def golden_subset(name, K=None):
     """(ctx-free inputs of the first K templates of a golden set, built once)"""
-    if name not in _volumes:
+    K = SUBSET[name] if K is None else K
+    if (name, K) not in _volumes:
         from mecat_amd import workload as W
         n, L, Gn, seed, ont, tech, mas = (int(x) for x in G[name + "_par"])
         err, ratio = (float(x) for x in G[name + "_ratio"])
         codes, lens = W.synth_reads(n, L, err, Gn, seed, ont)
         pac, offs, nb = W.pack_volume(codes, lens)
-        K = SUBSET[name]
         tb = G[name + "_tmpl_begin"][: K + 1].copy()
         starts = np.concatenate([[0], np.cumsum(lens.astype(np.int64))])
         letters = [LET[codes[starts[t]: starts[t + 1]]] for t in range(K)]
-        _volumes[name] = dict(pac=pac, offs=offs, nb=nb, lens=lens, K=K, tb=tb, cands=G[name + "_cands"][: tb[K]].copy(), tech=tech, mas=mas, ratio=ratio,
+        _volumes[name, K] = dict(pac=pac, offs=offs, nb=nb, lens=lens, K=K, tb=tb, cands=G[name + "_cands"][: tb[K]].copy(), tech=tech, mas=mas, ratio=ratio,
                               letters=letters, nacc=G[name + "_nacc"][:K], sha=G[name + "_sha"][:K], meta=G[name + "_meta"][: int(G[name + "_nacc"][:K].sum())])
-    return _volumes[name]
+    return _volumes[name, K]
 
 
-def run_ex(ctx, g, want, tb=None, cands=None):
+def run_ex(ctx, g, want, tb=None, cands=None, start_id=0):
     import mecat_amd.hip as M
-    vol = M.Volume(ctx, g["pac"], g["offs"], g["nb"], 0)
+    vol = M.Volume(ctx, g["pac"], g["offs"], g["nb"], start_id)
     try:
         out = M.cns_accept_templates_ex(ctx, vol, (g["cands"] if cands is None else cands).copy(), g["tb"] if tb is None else tb, g["tech"], g["mas"], g["ratio"],
                                         want, threads=16)
@@ -263,3 +271,140 @@ def test_the_old_entry_point_is_untouched(ctx, both):
     assert len(t1) == 0 and len(i1) == 0 and len(b1) == 0
     for acc, strings, nj in ((a1, s1, nj1), both["pacbio"][:3]):
         assert np.array_equal(acc0, acc) and bytes(str0) == strings.tobytes() and nj0 == nj
+
+
+# ---- against the compiled reference: tests/golden/cns_table.npz ---------------------------------------------------------------------
+FULL = {"pacbio": 240, "nanopore": 160}
+
+
+@pytest.mark.parametrize("name", sorted(FULL))
+def test_whole_golden_table_equals_the_reference(ctx, name):
+    """every template of the golden accept sets, CNS_WANT_TABLE alone: table and ident bytes are what the unmodified
+    consensus_one_read_can_* left in ConsensusThreadData::cns_table and what identify_one_consensus_item makes of it.  No restatement."""
+    import mecat_amd.hip as M
+    T = TG.golden()
+    n = FULL[name]
+    g = golden_subset(name, n)
+    assert g["K"] == n == len(g["lens"]) == len(T[name + "_table_sha"]) == len(T[name + "_ident_sha"])
+    acc, strings, njobs, table, ident, begin = run_ex(ctx, g, M.CNS_WANT_TABLE)
+    assert len(strings) == 0 and len(begin) == n + 1 and begin[0] == 0 and len(table) == len(ident) == begin[n]
+    assert np.array_equal(np.diff(begin), np.where(np.diff(g["tb"]) > 0, g["lens"], 0))
+    bad = []
+    for t in range(n):
+        if begin[t + 1] == begin[t]:
+            assert str(T[name + "_table_sha"][t]) == "" and str(T[name + "_ident_sha"][t]) == "", t      # no candidates, no table
+            continue
+        if (hashlib.sha256(table[begin[t]: begin[t + 1]].tobytes()).hexdigest() != str(T[name + "_table_sha"][t])
+                or hashlib.sha256(ident[begin[t]: begin[t + 1]].tobytes()).hexdigest() != str(T[name + "_ident_sha"][t])):
+            bad.append(t)
+    b8 = T[name + "_begin8"]
+    want_t, want_i = TG.planes_to_table(T[name + "_table8"]), T[name + "_ident8"]
+    assert np.array_equal(begin[:9], b8)
+    got_t, got_i = table[: b8[8]], ident[: b8[8]]
+    for f in R.TABLE_DTYPE.names:
+        assert np.array_equal(got_t[f], want_t[f]), (f, np.nonzero(got_t[f] != want_t[f])[0][:10])
+    assert np.array_equal(got_i, want_i), np.nonzero(got_i != want_i)[0][:10]
+    assert not bad, bad[:10]
+    assert int((np.diff(begin) > 0).sum()) == n          # every template of the set has a table: 240 + 160
+
+
+def test_ident_sweep_on_the_device(ctx):
+    """One hook call whose table holds every (mat, ins, del) with mat + ins <= 100 and del <= mat + ins once (348 551 positions, 100
+    alignments): positions sorted by cov = mat + ins descending; alignment a spans the positions with cov > a; at position p it has a
+    match column if a < mat[p], else an insertion column, and if a < del[p] one query base over a template gap behind it.  Counts must be
+    the intended ones, ident the compiled identify_one_consensus_item's (cns_table.npz sweep_ident), base the template letter exactly
+    where mat > 0.  Pins comparisons, thresholds and cov == 0, not rounding: over this domain double, float32 and exact integer
+    arithmetic agree."""
+    import mecat_amd.hip as M
+    tri = R.sweep_triples()
+    want_id = TG.golden()["sweep_ident"]
+    assert len(tri) == len(want_id) == 348551
+    cov = tri[:, 0] + tri[:, 1]
+    order = np.argsort(-cov, kind="stable")
+    mat, ins, dele = (np.ascontiguousarray(x) for x in tri[order].T)
+    covs = cov[order]
+    rng = np.random.default_rng(9)
+    tmpl = LET[rng.integers(0, 4, len(tri))]
+    alns = []
+    for a in range(R.MAX_CNS_OVLPS):
+        P = int((covs > a).sum())
+        m, d = a < mat[:P], a < dele[:P]
+        ncol = 1 + d.astype(np.int64)
+        at = np.cumsum(ncol) - ncol
+        q = np.full(int(ncol.sum()), R.GAP, dtype=np.uint8)
+        s = np.full(len(q), R.GAP, dtype=np.uint8)
+        s[at] = tmpl[:P]
+        q[at[m]] = tmpl[:P][m]
+        q[at[d] + 1] = LET[a % 4]
+        alns.append((q, s, 0))
+    assert len(alns[0][0]) > len(tri) and len(alns[-1][0]) >= 101
+    table, ident = M.debug_cns_table(ctx, *lay_out(alns), tmpl.tobytes())
+    for f, want in (("mat_cnt", mat), ("ins_cnt", ins), ("del_cnt", dele), ("base", np.where(mat > 0, tmpl, ord("N")))):
+        assert np.array_equal(table[f], want), (f, np.nonzero(table[f] != want)[0][:10])
+    assert np.array_equal(ident, want_id[order]), tri[order][np.nonzero(ident != want_id[order])[0][:10]]
+    assert int((covs == 0).sum()) == 1 and np.all(ident[covs == 0] == 7)
+
+
+def test_adversarial_pairs_equal_the_reference(ctx):
+    """every adversarial pair of cns_table.npz through the hook, each on a span of its own of a shared template: [guard][tmpl_len
+    positions][guard], as the harness laid the reference's table out, so that the whole block, guards included, must equal what
+    meap_add_one_aln left.  A pair with a run of template gaps in front of its first template base at soff == 0 goes to position 0 of a
+    call instead (one per call): there the device's table equals the reference's inside the array, and the reference's stray count is in
+    its front guard only.  Four leads shift the strings against the 64-byte grid, as test_gpu_cns_strings.py lays pushgaps.npz out."""
+    import mecat_amd.hip as M
+    pairs = TG.adversarial_pairs()
+    letters = [TG.template_of(s, soff, tl) for _, s, soff, tl, _ in pairs]
+    lead_run = [TG.leading_run(q, s) for q, s, _, _, _ in pairs]
+    zero = [i for i, p in enumerate(pairs) if p[2] == 0 and lead_run[i][0]]
+    rest = [i for i, p in enumerate(pairs) if not (p[2] == 0 and lead_run[i][0])]
+    ncalls = max(len(zero), -(-len(rest) // 254))
+    assert len(zero) >= 50 and len(pairs) >= 900 and sum(1 for i in zero if lead_run[i][1]) >= 20
+    strays = 0
+    for lead in (0, 1, 7, 13):
+        for c in range(ncalls):
+            members = ([zero[c]] if c < len(zero) else []) + rest[c::ncalls]
+            assert len(members) <= 255
+            alns, where, tmpl = [], [], []
+            pos = 0
+            for i in members:
+                q, s, soff, tl, _ = pairs[i]
+                at_zero = c < len(zero) and i == zero[c]
+                if not at_zero:
+                    tmpl.append(LET[:1])            # the front guard's position
+                    pos += 1
+                alns.append((q, s, pos + soff))
+                where.append(pos)
+                tmpl += [letters[i], LET[:1]]       # ... and the back guard's
+                pos += tl + 1
+            tmpl = np.concatenate(tmpl)
+            assert len(tmpl) == pos
+            table, _ = M.debug_cns_table(ctx, *lay_out(alns, lead), tmpl.tobytes())
+            for i, w in zip(members, where):
+                q, s, soff, tl, want = pairs[i]
+                if w == 0:                          # the pair at position 0: no index -1 on the device
+                    assert table[: tl + 1].tobytes() == want[1:].tobytes(), (lead, i)
+                    assert int(want[0]["del_cnt"]) == (1 if lead_run[i][1] else 0) and want[0]["mat_cnt"] == want[0]["ins_cnt"] == 0, i
+                    strays += int(want[0]["del_cnt"])
+                else:
+                    got = table[w - 1: w + tl + 1]
+                    assert got.tobytes() == want.tobytes(), (lead, i, np.nonzero(got.view(np.uint32) != want.view(np.uint32))[0][:10])
+    assert strays >= 4 * 20
+
+
+def test_volume_whose_first_read_id_is_not_zero(ctx, both):
+    """read ids are volume-wide numbers (include/mecat_hip.h: local index = id - start_read_id): the same reads as a volume that starts
+    at read 70 001, candidates shifted by as much, give the same bytes — cns_table_finish looks the template's letters up by sid - start"""
+    import mecat_amd.hip as M
+    start = 70001
+    for name in sorted(SUBSET):
+        g = golden_subset(name)
+        acc, strings, njobs, table, ident, begin = both[name]
+        cands = g["cands"].copy()
+        cands[:, 1] += start
+        cands[:, 7] += start
+        a2, s2, nj2, t2, i2, b2 = run_ex(ctx, g, M.CNS_WANT_STRINGS | M.CNS_WANT_TABLE, cands=cands, start_id=start)
+        assert t2.tobytes() == table.tobytes() and i2.tobytes() == ident.tobytes() and np.array_equal(b2, begin)
+        assert s2.tobytes() == strings.tobytes() and nj2 == njobs
+        assert np.array_equal(a2["qid"], acc["qid"] + start) and np.array_equal(a2["sid"], acc["sid"] + start)
+        assert all(np.array_equal(a2[f], acc[f]) for f in acc.dtype.names if f not in ("qid", "sid"))
+        assert (table["mat_cnt"] > 0).sum() > 1000 and len(set(table["base"][table["mat_cnt"] > 0].tolist())) == 4
