@@ -377,7 +377,8 @@ int  mhip_debug_push_gaps(mhip_ctx* ctx, char* buf, int64_t bytes, const int64_t
  * With MHIP_CNS_WANT_TABLE alone the strings are built on the device (the tally reads them) but never copied: *out_strings is NULL,
  * *out_strings_bytes 0 and str_offset -1 in every accepted record.  want == 0 is an error.  Outputs that were not asked for come back
  * NULL (their pointers may be NULL then); all are released with mhip_cns_free.  Counts are bytes: at most 60 / 100 alignments are
- * accepted per template, so none overflows.  Effective ranges, segment cutting and the POA refinement stay with the caller. */
+ * accepted per template, so none overflows.  Effective ranges and segment cutting: mhip_cns_accept_templates_plan below; the POA
+ * refinement stays with the caller. */
 typedef struct { uint8_t base, mat_cnt, ins_cnt, del_cnt; } mhip_cns_table_item;   /* CnsTableItem */
 #define MHIP_CNS_WANT_STRINGS 1
 #define MHIP_CNS_WANT_TABLE   2     /* table + ident */
@@ -392,6 +393,46 @@ int  mhip_cns_accept_templates_ex(mhip_ctx* ctx, const mhip_volume* vol, mhip_ex
  * [0, tmpl_len).  -> table_out[tmpl_len], ident_out[tmpl_len] */
 int  mhip_debug_cns_table(mhip_ctx* ctx, const char* buf, int64_t bytes, const int64_t* off, const int32_t* len, const int32_t* soff,
                           int n_pairs, const char* tmpl_letters, int tmpl_len, mhip_cns_table_item* table_out, uint8_t* ident_out);
+/* ---- mecat2cns' consensus plan, built in the accept stage behind the table (cns_plan.hip): what consensus_one_read_can_* decides from
+ * the table alone.  Per template, with its read length L, the table, the ident bytes and the (soff, send) of its accepted alignments:
+ *   effective ranges   tech 1: the one range (0, L) (mecat_correction.cpp:509; :357).  tech 0: get_effective_ranges (:118-153) — nothing
+ *                      accepted: no range; an alignment with start <= 500 and L - end <= 500: the one range (0, L); otherwise the sweep over
+ *                      the alignments sorted by (start asc, end desc), a range kept when right - left >= min_size * 0.95 (in double).  A
+ *                      template without candidates has no table and no range.
+ *   segments           consensus_worker (:203-239): inside every effective range, in order, each maximal run of positions with
+ *                      mat_cnt + ins_cnt >= min_cov whose length satisfies end - beg >= 0.95 * min_size (in double).  A run does not
+ *                      continue from one range into the next, even where they touch.
+ *   windows            meap_consensus_one_segment (:81-108), inside a segment [beg, end): anchors are the positions with FMAT; from an
+ *                      anchor i to the next anchor j (the segment's end if there is none) the window (sb = i, se = j) is listed when some
+ *                      position of [i, j) has UNDS or FDEL — these are the stretches the reference hands to meap_cns_one_indel, with
+ *                      cov = mat_cnt + ins_cnt at i as its min_cov (:103).  Positions in front of the first anchor belong to no window.
+ * The mecat2cns defaults are min_cov 4 / min_size 5000 (PacBio) and 6 / 2000 (nanopore); min_size >= 2 and min_cov >= 1 are required.
+ * Segments come in template order, then ascending beg: template t owns out_segments[out_seg_begin[t] .. out_seg_begin[t + 1]).  Windows
+ * come in segment order, then ascending sb: segment s owns out_windows[win_begin .. win_end).  Effective ranges are (start, end) pairs:
+ * template t owns pairs out_erange_begin[t] .. out_erange_begin[t + 1].  The output is the same bytes on every run.
+ * mhip_cns_accept_templates_plan is mhip_cns_accept_templates_ex with MHIP_CNS_WANT_PLAN allowed in `want`: the plan needs the table, so
+ * the table is built on the device whether or not MHIP_CNS_WANT_TABLE is set, but it is copied to the host only with that bit; with
+ * MHIP_CNS_WANT_PLAN alone neither strings nor tables cross the PCIe link.  Without MHIP_CNS_WANT_PLAN the six plan outputs come back
+ * NULL / 0 (their pointers may be NULL then) and min_cov / min_size are not looked at.  All buffers are released with mhip_cns_free.
+ * Retrieving the windows' substrings, the POA and the output of the corrected reads stay with the caller. */
+typedef struct { int32_t template_index, beg, end, n_anchors; int64_t win_begin, win_end; } mhip_cns_segment;
+typedef struct { int32_t sb, se, cov, segment; } mhip_cns_window;       /* segment: index into out_segments */
+#define MHIP_CNS_WANT_PLAN 4
+int  mhip_cns_accept_templates_plan(mhip_ctx* ctx, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin,
+                                    int num_templates, int tech, int min_align_size, double min_mapping_ratio, int num_threads, int want,
+                                    int min_cov, int min_size, mhip_cns_accepted** out_accepted, int64_t* out_count, char** out_strings,
+                                    int64_t* out_strings_bytes, int64_t* out_jobs, mhip_cns_table_item** out_table, uint8_t** out_ident,
+                                    int64_t** out_table_begin /* [num_templates + 1] */, mhip_cns_segment** out_segments,
+                                    int64_t** out_seg_begin /* [num_templates + 1] */, mhip_cns_window** out_windows, int64_t* out_n_windows,
+                                    int32_t** out_eranges, int64_t** out_erange_begin /* [num_templates + 1] */);
+/* test hook: the same host range function and the same plan kernels on host-supplied tables.  Template k owns table / ident
+ * [table_begin[k], table_begin[k + 1]) and the mapping ranges (soff, send) ranges[2 r], ranges[2 r + 1] for r in [range_begin[k],
+ * range_begin[k + 1]); both begin arrays have n_tmpl + 1 entries and start at 0.  The ident bytes are taken as given (they need not be
+ * what the counts would give).  Refused: a mapping range that leaves its template.  Outputs as above. */
+int  mhip_debug_cns_plan(mhip_ctx* ctx, const mhip_cns_table_item* table, const uint8_t* ident, const int64_t* table_begin, int n_tmpl,
+                         const int32_t* ranges, const int64_t* range_begin, int tech, int min_cov, int min_size,
+                         mhip_cns_segment** out_segments, int64_t** out_seg_begin, mhip_cns_window** out_windows, int64_t* out_n_windows,
+                         int32_t** out_eranges, int64_t** out_erange_begin);
 /* mhip_cns_free does not return a string buffer to the system at once: the library keeps the LARGEST released one (gigabytes — about
  * 14 GB for a config-2-sized batch) and hands it out again to the next batch that fits, because first-touching fresh pages costs
  * more than the batch's GPU time.  The parked buffer belongs to the process, not to a context (mhip_ctx_destroy leaves it).  This call

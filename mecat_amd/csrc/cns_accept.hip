@@ -17,6 +17,9 @@
 // mhip_cns_accept_templates_ex adds what the reference does with those strings first: the consensus table of every template
 // (meap_add_one_aln, :36-60, at :439 / :502) and its per-position classification (identify_one_consensus_item, :14-24), tallied
 // from the strings while they are still in device memory (cns_table.hip) — and, asked for the table alone, never copies the strings.
+// mhip_cns_accept_templates_plan adds what the reference decides from the table alone: the effective ranges (get_effective_ranges,
+// :118-153, in the replay: cns_ranges.h), and behind a slice's table kernels the segments (consensus_worker, :203-239) and the windows
+// that go to the POA (meap_consensus_one_segment, :81-108) — cns_plan.hip.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -34,6 +37,8 @@
 
 #include "common.h"
 #include "cns_strings.h"
+#include "cns_plan.h"
+#include "cns_ranges.h"
 #include "cns_table.h"
 
 namespace {
@@ -156,12 +161,22 @@ void mhip_cns_release_parked(void) {
     strbuf_free(p);
 }
 
-// the body of both entry points; want_tab: the outputs behind out_jobs are filled as well
+// what mhip_cns_accept_templates_plan adds to the call
+struct PlanArgs {
+    bool want = false;
+    int min_cov = 0, min_size = 0;
+    mhip_cns_segment** seg = nullptr; int64_t** seg_begin = nullptr; mhip_cns_window** win = nullptr; int64_t* n_win = nullptr;
+    int32_t** er = nullptr; int64_t** er_begin = nullptr;
+};
+
+// the body of the entry points; want_tab: the outputs behind out_jobs are filled as well; plan.want: the outputs of `plan` too
 static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin,
                            int num_templates, int tech, int min_align_size, double min_mapping_ratio, int num_threads, const bool want_str, const bool want_tab,
                            mhip_cns_accepted** out_accepted, int64_t* out_count, char** out_strings, int64_t* out_strings_bytes,
-                           int64_t* out_jobs, mhip_cns_table_item** out_table, uint8_t** out_ident, int64_t** out_table_begin) {
+                           int64_t* out_jobs, mhip_cns_table_item** out_table, uint8_t** out_ident, int64_t** out_table_begin, const PlanArgs& plan) {
     HIPCHK(hipSetDevice(c->device));
+    const bool want_plan = plan.want, build_tab = want_tab || want_plan;      // the plan reads the table: built on the device either way, copied only when asked for
+    const int min_run = want_plan ? cns_plan_min_run(plan.min_size) : 0;
     *out_accepted = nullptr; *out_count = 0; *out_strings = nullptr; *out_strings_bytes = 0;
     if (out_jobs) *out_jobs = 0;
     if (num_templates <= 0) return 0;
@@ -203,7 +218,7 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
 
     // the tables: one word per base of every template that has candidates, template after template
     std::vector<int64_t> TB;
-    if (want_tab) {
+    if (build_tab) {
         TB.assign((size_t)num_templates + 1, 0);
         for (int t = 0; t < num_templates; ++t)
             TB[(size_t)t + 1] = TB[(size_t)t] + (tmpl_begin[t + 1] > tmpl_begin[t] ? (int64_t)vol->h_offs[(size_t)(cands[tmpl_begin[t]].sid - start_id)].size : 0);
@@ -227,6 +242,63 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
         tab_out.tab = nullptr; tab_out.id = nullptr; tab_out.begin = nullptr;
         return 0;
     };
+    // the plan: effective ranges from the replay, segments and windows slice by slice in buffers of their own (their sizes are known
+    // slice by slice only), put together at the end; the records are final when they leave the device
+    struct PlanPiece { void* seg = nullptr; void* win = nullptr; int64_t nseg = 0, nwin = 0; long long bad = 0; };
+    // (bad: CnsPlanDev::d_bad, copied with the windows and looked at in hand_over_plan only, after every slice has run: the plan is refused
+    // there; an overflow of the segment slots is refused by cns_plan_launch at once)
+    struct PlanOut {
+        std::vector<PlanPiece> pieces;
+        ~PlanOut() { for (PlanPiece& p : pieces) { mhip_cns_free(p.seg); mhip_cns_free(p.win); } }
+    } plan_out;
+    std::vector<int64_t> SB, ERB;                 // per template: first segment; effective ranges (counts until the hand-over)
+    std::vector<int32_t> ER;
+    int64_t seg_total = 0, win_total = 0;
+    if (want_plan) { SB.assign((size_t)num_templates + 1, 0); ERB.assign((size_t)num_templates + 1, 0); }
+    auto hand_over_plan = [&]() -> int {          // (after the last copy has landed)
+        const size_t n1 = (size_t)num_templates + 1;
+        for (const PlanPiece& p : plan_out.pieces)
+            if (p.bad) { mhip_set_error("cns plan: the windows written are not the windows counted"); return -1; }
+        int64_t* sb = (int64_t*)malloc(sizeof(int64_t) * n1);
+        int64_t* eb = (int64_t*)malloc(sizeof(int64_t) * n1);
+        int32_t* er = (int32_t*)malloc(std::max<size_t>(sizeof(int32_t) * ER.size(), 1));
+        void *seg = nullptr, *win = nullptr;
+        if (plan_out.pieces.size() == 1) {
+            seg = plan_out.pieces[0].seg; win = plan_out.pieces[0].win;
+            plan_out.pieces.clear();
+        } else {
+            seg = result_alloc(sizeof(mhip_cns_segment) * (size_t)seg_total, num_threads);
+            win = result_alloc(sizeof(mhip_cns_window) * (size_t)win_total, num_threads);
+        }
+        if (!sb || !eb || !er || !seg || !win) { free(sb); free(eb); free(er); mhip_cns_free(seg); mhip_cns_free(win); mhip_set_error("out of memory"); return -1; }
+        size_t so = 0, wo = 0;
+        for (PlanPiece& p : plan_out.pieces) {
+            const size_t sbytes = sizeof(mhip_cns_segment) * (size_t)p.nseg, wbytes = sizeof(mhip_cns_window) * (size_t)p.nwin, piece = (size_t)64 << 20;
+            if (sbytes) memcpy((char*)seg + so, p.seg, sbytes);
+            parallel_for((int64_t)((wbytes + piece - 1) / piece), num_threads, [&](int64_t pc) {
+                const size_t o = (size_t)pc * piece;
+                memcpy((char*)win + wo + o, (const char*)p.win + o, std::min(piece, wbytes - o));
+            });
+            so += sbytes; wo += wbytes;
+        }
+        memcpy(sb, SB.data(), sizeof(int64_t) * n1);
+        eb[0] = 0;
+        for (size_t t = 0; t + 1 < n1; ++t) eb[t + 1] = eb[t] + ERB[t + 1];
+        if (!ER.empty()) memcpy(er, ER.data(), sizeof(int32_t) * ER.size());
+        *plan.seg = (mhip_cns_segment*)seg; *plan.seg_begin = sb; *plan.win = (mhip_cns_window*)win; *plan.n_win = win_total; *plan.er = er; *plan.er_begin = eb;
+        return 0;
+    };
+    auto hand_over = [&]() -> int {
+        if (want_tab && hand_over_tables()) return -1;
+        const double t_put = now();
+        const int plan_rc = want_plan ? hand_over_plan() : 0;
+        tk[7] += now() - t_put;
+        if (plan_rc) {
+            if (want_tab) { mhip_cns_free(*out_table); mhip_cns_free(*out_ident); mhip_cns_free(*out_table_begin); *out_table = nullptr; *out_ident = nullptr; *out_table_begin = nullptr; }
+            return -1;
+        }
+        return 0;
+    };
 
     lap(0);
     // 2. the first <= 200 candidates of every template, as alignment jobs
@@ -234,7 +306,7 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
     for (int t = 0; t < num_templates; ++t) jfirst[(size_t)t + 1] = jfirst[(size_t)t] + std::min<int64_t>(max_ext, tmpl_begin[t + 1] - tmpl_begin[t]);
     const int64_t nj = jfirst[(size_t)num_templates];
     if (out_jobs) *out_jobs = nj;
-    if (nj == 0) return want_tab ? hand_over_tables() : 0;
+    if (nj == 0) return hand_over();
     if (nj > 0x7fffffffLL) { mhip_set_error("cns accept: too many jobs in one batch"); return -1; }
     std::vector<mhip_aln_job> jobs((size_t)nj);
     parallel_for(num_templates, num_threads, [&](int64_t t) {
@@ -343,6 +415,7 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
         std::vector<int64_t> afirst;               // per template: first accepted record of the slice
         std::vector<CnsStrItem> items;
         size_t sbytes = 0;
+        std::vector<std::vector<int32_t>> er;      // per template: effective ranges, (start, end) pairs (with the plan only)
     };
     std::vector<mhip_cns_accepted> Avec;
     lap(1);
@@ -357,6 +430,7 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
     auto replay_slice = [&](Slice& sl) {
         const int nt = sl.t1 - sl.t0;
         sl.acc.assign((size_t)nt, std::vector<int32_t>());
+        sl.er.assign((size_t)(want_plan ? nt : 0), std::vector<int32_t>());
         parallel_for(nt, num_threads, [&](int64_t tl) {
             const int64_t t = sl.t0 + tl;
             const int64_t b = tmpl_begin[t], n = tmpl_begin[t + 1] - b;
@@ -382,6 +456,11 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
                 used.insert(ec.qid);
                 sl.acc[(size_t)tl].push_back((int32_t)ji);
             }
+            if (want_plan) {                                         // cns_vec.get_mapping_ranges + get_effective_ranges, :445-447 (tech 1: :509)
+                std::vector<std::pair<int32_t, int32_t>> mr;
+                for (const int32_t ji : sl.acc[(size_t)tl]) mr.emplace_back(res[(size_t)ji].soff, res[(size_t)ji].send);
+                cns_effective_ranges(mr, ssize, tech, plan.min_size, sl.er[(size_t)tl]);
+            }
         });
         sl.afirst.assign((size_t)nt + 1, 0);
         for (int tl = 0; tl < nt; ++tl) sl.afirst[(size_t)tl + 1] = sl.afirst[(size_t)tl] + (int64_t)sl.acc[(size_t)tl].size();
@@ -404,7 +483,8 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
     // slice's tables (whole templates: a contiguous piece of the output) zeroed, tallied from the strings and finished behind them
     auto strings_slice = [&](Slice& sl, int b, int k) -> int {
         const int64_t na = (int64_t)sl.items.size();
-        const int64_t tw0 = want_tab ? TB[(size_t)sl.t0] : 0, tw = want_tab ? TB[(size_t)sl.t1] - tw0 : 0;
+        const int64_t tw0 = build_tab ? TB[(size_t)sl.t0] : 0, tw = build_tab ? TB[(size_t)sl.t1] - tw0 : 0;
+        if (want_plan) for (int t = sl.t0; t <= sl.t1; ++t) SB[(size_t)t] = seg_total;      // (what a slice without a table leaves)
         if (na == 0 && tw == 0) return 0;
         if (want_str && na) {
             size_t want = S_used + sl.sbytes;
@@ -412,7 +492,7 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
                 want = std::max(want, (size_t)((double)want / (double)sl.t1 * (double)num_templates * est_scale) + ((size_t)1 << 20));
             if (s_reserve(want)) return -1;
         }
-        std::vector<CnsTabItem> titems((size_t)(want_tab ? na : 0));
+        std::vector<CnsTabItem> titems((size_t)(build_tab ? na : 0));
         // the accepted records (what the caller gets beside the strings)
         const size_t a0 = Avec.size();
         Avec.resize(a0 + (size_t)na);
@@ -430,7 +510,7 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
                 o.qoff = r.qoff; o.qend = r.qend; o.soff = r.soff; o.send = r.send;
                 o.aln_size = it.aln_size;
                 o.str_offset = want_str ? (int64_t)(S_used + it.off) : -1;
-                if (want_tab) {
+                if (build_tab) {
                     CnsTabItem& ti = titems[(size_t)(sl.afirst[(size_t)tl] + (int64_t)kk)];
                     ti.off = it.off; ti.tab = (unsigned long long)(TB[(size_t)t] - tw0); ti.aln_size = it.aln_size; ti.soff = r.soff;
                     ti.tab_len = (int32_t)(TB[(size_t)t + 1] - TB[(size_t)t]); ti.pad = 0;
@@ -475,13 +555,39 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
             HIPCHK(hipMemcpyAsync(d_voloff, voloff.data(), sizeof(int32_t) * (size_t)ntm, hipMemcpyHostToDevice, c->stream));
             if (cns_table_launch(c, vol, d_str, d_titems, (int)na, d_tab, d_id, (long long)tw, d_first, d_voloff, ntm, nullptr)) return -1;
         }
+        // the slice's plan, behind cns_table_finish on the same stream and in front of the copies
+        CnsPlanDev pd;
+        PlanPiece piece;
+        if (want_plan && tw) {
+            const int nt = sl.t1 - sl.t0;
+            std::vector<long long> tbl((size_t)nt + 1), rbl((size_t)nt + 1, 0);
+            std::vector<int32_t> erl;
+            for (int tl = 0; tl <= nt; ++tl) tbl[(size_t)tl] = (long long)(TB[(size_t)(sl.t0 + tl)] - tw0);
+            for (int tl = 0; tl < nt; ++tl) {
+                erl.insert(erl.end(), sl.er[(size_t)tl].begin(), sl.er[(size_t)tl].end());
+                rbl[(size_t)tl + 1] = (long long)(erl.size() / 2);
+                ERB[(size_t)(sl.t0 + tl) + 1] = (int64_t)(sl.er[(size_t)tl].size() / 2);
+            }
+            ER.insert(ER.end(), erl.begin(), erl.end());
+            if (cns_plan_launch(c, b, d_tab, d_id, nt, sl.t0, tbl.data(), erl.data(), rbl.data(), plan.min_cov, min_run, seg_total, win_total, SB.data() + sl.t0, &pd)) return -1;
+            tk[6] += pd.wait_s;
+            piece.nseg = pd.nseg; piece.nwin = pd.nwin;
+            piece.seg = result_alloc(sizeof(mhip_cns_segment) * (size_t)pd.nseg, num_threads);
+            piece.win = result_alloc(sizeof(mhip_cns_window) * (size_t)pd.nwin, num_threads);
+            plan_out.pieces.push_back(piece);
+            if (!piece.seg || !piece.win) { mhip_set_error("out of memory (%lld windows)", (long long)pd.nwin); return -1; }
+            seg_total += pd.nseg; win_total += pd.nwin;
+        }
         HIPCHK(hipEventRecord(ev_built[b], c->stream));
         HIPCHK(hipStreamWaitEvent(copy_stream, ev_built[b], 0));
         if (want_str && na) {
             HIPCHK(hipMemcpyAsync(S + S_used, d_str, sl.sbytes, hipMemcpyDeviceToHost, copy_stream));
             S_used += sl.sbytes;
         }
-        if (tw) {
+        if (pd.nseg) HIPCHK(hipMemcpyAsync(piece.seg, pd.d_seg, sizeof(mhip_cns_segment) * (size_t)pd.nseg, hipMemcpyDeviceToHost, copy_stream));
+        if (pd.nwin) HIPCHK(hipMemcpyAsync(piece.win, pd.d_win, sizeof(mhip_cns_window) * (size_t)pd.nwin, hipMemcpyDeviceToHost, copy_stream));
+        if (pd.d_bad) HIPCHK(hipMemcpyAsync(&plan_out.pieces.back().bad, pd.d_bad, sizeof(long long), hipMemcpyDeviceToHost, copy_stream));      // (pieces: reserved, nothing moves)
+        if (tw && want_tab) {
             HIPCHK(hipMemcpyAsync(tab_out.tab + tw0, d_tab, sizeof(uint32_t) * (size_t)tw, hipMemcpyDeviceToHost, copy_stream));
             HIPCHK(hipMemcpyAsync(tab_out.id + tw0, d_id, (size_t)tw, hipMemcpyDeviceToHost, copy_stream));
         }
@@ -490,6 +596,7 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
     };
 
     std::vector<Slice> slices((size_t)nslices);
+    plan_out.pieces.reserve((size_t)nslices);
     for (int k = 0; k < nslices; ++k) {
         Slice& sl = slices[(size_t)k];
         sl.t0 = sl_t[(size_t)k]; sl.t1 = sl_t[(size_t)k + 1];
@@ -513,11 +620,11 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
     }
     HIPCHK(hipStreamSynchronize(copy_stream));
     const int64_t na = (int64_t)Avec.size();
-    if (na == 0) return want_tab ? hand_over_tables() : 0;
+    if (na == 0) return hand_over();
     mhip_cns_accepted* A = (mhip_cns_accepted*)malloc(sizeof(mhip_cns_accepted) * (size_t)na);
     if (!A) { mhip_set_error("out of memory"); return -1; }
     memcpy(A, Avec.data(), sizeof(mhip_cns_accepted) * (size_t)na);
-    if (want_tab && hand_over_tables()) { free(A); return -1; }
+    if (hand_over()) { free(A); return -1; }
     const int64_t sbytes = (int64_t)S_used;
     s_guard.armed = false;
     lap(5);
@@ -525,6 +632,9 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
         fprintf(stderr, "[cns_accept] %d templates, %lld jobs in %d slices, %lld accepted, %.2f GB of strings: sort + checks %.3f s, jobs %.3f, re-alignment on the "
                         "device %.3f, accept replay beyond it %.3f, strings launched %.3f, last copies %.3f\n", num_templates, (long long)nj, nslices, (long long)na,
                 (double)sbytes / 1e9, tk[0], tk[1], tk[2], tk[3], tk[4], tk[5]);
+    if (times && want_plan)
+        fprintf(stderr, "[cns_accept] plan: %lld segments, %lld windows: waited for the counts %.3f s (within strings launched), slices' pieces put together %.3f (within last copies)\n",
+                (long long)seg_total, (long long)win_total, tk[6], tk[7]);
     *out_accepted = A;
     *out_count = na;
     *out_strings = S;
@@ -537,7 +647,7 @@ int mhip_cns_accept_templates(mhip_ctx* c, const mhip_volume* vol, const uint8_t
                               mhip_cns_accepted** out_accepted, int64_t* out_count, char** out_strings, int64_t* out_strings_bytes,
                               int64_t* out_jobs) {
     return cns_accept_body(c, vol, cands, tmpl_begin, num_templates, tech, min_align_size, min_mapping_ratio, num_threads, true, false, out_accepted, out_count,
-                           out_strings, out_strings_bytes, out_jobs, nullptr, nullptr, nullptr);
+                           out_strings, out_strings_bytes, out_jobs, nullptr, nullptr, nullptr, PlanArgs());
 }
 
 int mhip_cns_accept_templates_ex(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin, int num_templates, int tech,
@@ -551,7 +661,40 @@ int mhip_cns_accept_templates_ex(mhip_ctx* c, const mhip_volume* vol, mhip_ext_c
     if (out_ident) *out_ident = nullptr;
     if (out_table_begin) *out_table_begin = nullptr;
     return cns_accept_body(c, vol, cands, tmpl_begin, num_templates, tech, min_align_size, min_mapping_ratio, num_threads, (want & MHIP_CNS_WANT_STRINGS) != 0, want_tab,
-                           out_accepted, out_count, out_strings, out_strings_bytes, out_jobs, out_table, out_ident, out_table_begin);
+                           out_accepted, out_count, out_strings, out_strings_bytes, out_jobs, out_table, out_ident, out_table_begin, PlanArgs());
+}
+
+int mhip_cns_accept_templates_plan(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin, int num_templates, int tech,
+                                   int min_align_size, double min_mapping_ratio, int num_threads, int want, int min_cov, int min_size,
+                                   mhip_cns_accepted** out_accepted, int64_t* out_count, char** out_strings, int64_t* out_strings_bytes, int64_t* out_jobs,
+                                   mhip_cns_table_item** out_table, uint8_t** out_ident, int64_t** out_table_begin, mhip_cns_segment** out_segments,
+                                   int64_t** out_seg_begin, mhip_cns_window** out_windows, int64_t* out_n_windows, int32_t** out_eranges, int64_t** out_erange_begin) {
+    const bool want_tab = (want & MHIP_CNS_WANT_TABLE) != 0;
+    PlanArgs plan;
+    plan.want = (want & MHIP_CNS_WANT_PLAN) != 0;
+    if (want == 0 || (want & ~(MHIP_CNS_WANT_STRINGS | MHIP_CNS_WANT_TABLE | MHIP_CNS_WANT_PLAN))) {
+        mhip_set_error("cns accept: want = %d (MHIP_CNS_WANT_STRINGS | MHIP_CNS_WANT_TABLE | MHIP_CNS_WANT_PLAN)", want);
+        return -1;
+    }
+    if (want_tab && (!out_table || !out_ident || !out_table_begin)) { mhip_set_error("cns accept: the table was asked for without a place to put it"); return -1; }
+    if (plan.want && (!out_segments || !out_seg_begin || !out_windows || !out_n_windows || !out_eranges || !out_erange_begin)) {
+        mhip_set_error("cns accept: the plan was asked for without a place to put it");
+        return -1;
+    }
+    if (plan.want && (min_size < 2 || min_cov < 1)) { mhip_set_error("cns accept: the plan needs min_size >= 2 and min_cov >= 1 (%d, %d)", min_size, min_cov); return -1; }
+    if (out_table) *out_table = nullptr;
+    if (out_ident) *out_ident = nullptr;
+    if (out_table_begin) *out_table_begin = nullptr;
+    if (out_segments) *out_segments = nullptr;
+    if (out_seg_begin) *out_seg_begin = nullptr;
+    if (out_windows) *out_windows = nullptr;
+    if (out_n_windows) *out_n_windows = 0;
+    if (out_eranges) *out_eranges = nullptr;
+    if (out_erange_begin) *out_erange_begin = nullptr;
+    plan.min_cov = min_cov; plan.min_size = min_size;
+    plan.seg = out_segments; plan.seg_begin = out_seg_begin; plan.win = out_windows; plan.n_win = out_n_windows; plan.er = out_eranges; plan.er_begin = out_erange_begin;
+    return cns_accept_body(c, vol, cands, tmpl_begin, num_templates, tech, min_align_size, min_mapping_ratio, num_threads, (want & MHIP_CNS_WANT_STRINGS) != 0, want_tab,
+                           out_accepted, out_count, out_strings, out_strings_bytes, out_jobs, out_table, out_ident, out_table_begin, plan);
 }
 
 }  // extern "C"

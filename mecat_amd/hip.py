@@ -125,6 +125,11 @@ def lib():
     L.mhip_cns_accept_templates_ex.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_double, i32, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp),
                                                C.POINTER(i64), C.POINTER(i64), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.mhip_debug_cns_table.argtypes = [vp, vp, i64, vp, vp, vp, i32, vp, i32, vp, vp]
+    L.mhip_cns_accept_templates_plan.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_double, i32, i32, i32, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp),
+                                                 C.POINTER(i64), C.POINTER(i64), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                                 C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(vp)]
+    L.mhip_debug_cns_plan.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(vp),
+                                      C.POINTER(vp)]
     L.mhip_cns_free.argtypes = [vp]
     L.mhip_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
     L.mhip_host_free.argtypes = [vp]
@@ -519,6 +524,77 @@ def debug_cns_table(ctx, buf, off, lens, soff, tmpl_letters):
     _chk(lib().mhip_debug_cns_table(ctx.h, buf.ctypes.data, len(buf), off.ctypes.data, lens.ctypes.data, soff.ctypes.data, len(off), let.ctypes.data, len(let),
                                     table.ctypes.data, ident.ctypes.data))
     return table, ident
+
+
+CNS_WANT_PLAN = 4
+SEGMENT_DTYPE = np.dtype([("template_index", np.int32), ("beg", np.int32), ("end", np.int32), ("n_anchors", np.int32), ("win_begin", np.int64),
+                          ("win_end", np.int64)])                                                                    # mhip_cns_segment
+WINDOW_DTYPE = np.dtype([("sb", np.int32), ("se", np.int32), ("cov", np.int32), ("segment", np.int32)])              # mhip_cns_window
+assert SEGMENT_DTYPE.itemsize == 32 and WINDOW_DTYPE.itemsize == 16
+
+
+def _cns_take(ptr, dtype, n):
+    """a copy of n records behind a pointer of the library (NULL: none), which is released"""
+    if ptr.value and n:
+        a = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(n * np.dtype(dtype).itemsize,)).view(dtype).copy()
+    else:
+        a = np.zeros(0, dtype)
+    lib().mhip_cns_free(ptr)
+    return a
+
+
+def _cns_plan_out(seg, segb, win, nwin, er, erb, ntmpl):
+    """the six plan outputs -> dict(segments, seg_begin, windows, eranges [k, 2], erange_begin).  Segments and windows are arrays over the
+    library's buffers (gigabytes of windows at config 2: no copy), released when they go; the small ones are copied and released"""
+    seg_begin = _cns_take(segb, np.int64, ntmpl + 1)
+    erange_begin = _cns_take(erb, np.int64, ntmpl + 1)
+    nseg = int(seg_begin[-1]) if len(seg_begin) else 0
+    ner = int(erange_begin[-1]) if len(erange_begin) else 0
+    return dict(segments=_cns_buffer(seg, nseg * SEGMENT_DTYPE.itemsize).view(SEGMENT_DTYPE), seg_begin=seg_begin,
+                windows=_cns_buffer(win, int(nwin.value) * WINDOW_DTYPE.itemsize).view(WINDOW_DTYPE),
+                eranges=_cns_take(er, np.int32, 2 * ner).reshape(-1, 2), erange_begin=erange_begin)
+
+
+def cns_accept_templates_plan(ctx, vol, cands, tmpl_begin, tech, min_align_size, min_mapping_ratio, want, min_cov, min_size, threads=8):
+    """cns_accept_templates_ex with CNS_WANT_PLAN allowed in `want`: the consensus plan of every template, computed on the device behind
+    its table — effective ranges (get_effective_ranges), the segments consensus_worker would correct (runs of mat_cnt + ins_cnt >= min_cov
+    of at least 0.95 * min_size positions inside an effective range) and per segment the windows meap_consensus_one_segment hands to the
+    POA (anchor to next anchor, some position in between UNDS or FDEL).  The mecat2cns defaults: min_cov 4 / min_size 5000 (PacBio),
+    6 / 2000 (nanopore).  -> cns_accept_templates_ex's tuple + a dict: segments [SEGMENT_DTYPE] in template order then ascending beg,
+    seg_begin [templates + 1], windows [WINDOW_DTYPE] in segment order then ascending sb (segment s owns windows[win_begin: win_end]),
+    eranges [k, 2], erange_begin [templates + 1]; None without CNS_WANT_PLAN.  With CNS_WANT_PLAN alone neither strings nor tables are
+    copied from the device."""
+    cands = np.ascontiguousarray(cands)
+    tb = np.ascontiguousarray(tmpl_begin, dtype=np.int64)
+    acc, st, tab, idn, tbeg = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    seg, segb, win, er, erb = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    na, sb, nj, nwin = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    _chk(lib().mhip_cns_accept_templates_plan(ctx.h, vol.h, cands.ctypes.data, tb.ctypes.data, len(tb) - 1, tech, min_align_size, float(min_mapping_ratio), threads,
+                                              int(want), int(min_cov), int(min_size), C.byref(acc), C.byref(na), C.byref(st), C.byref(sb), C.byref(nj), C.byref(tab),
+                                              C.byref(idn), C.byref(tbeg), C.byref(seg), C.byref(segb), C.byref(win), C.byref(nwin), C.byref(er), C.byref(erb)))
+    a = _cns_take(acc, ACCEPTED_DTYPE, na.value)
+    s = _cns_buffer(st, sb.value)
+    begin = _cns_take(tbeg, np.int64, len(tb))
+    nw = int(begin[-1]) if len(begin) else 0
+    plan = _cns_plan_out(seg, segb, win, nwin, er, erb, len(tb) - 1) if int(want) & CNS_WANT_PLAN else None
+    return a, s, nj.value, _cns_buffer(tab, 4 * nw).view(TABLE_DTYPE), _cns_buffer(idn, nw), begin, plan
+
+
+def debug_cns_plan(ctx, table, ident, table_begin, ranges, range_begin, tech, min_cov, min_size):
+    """test hook: the plan's host range function and kernels on host-supplied tables.  table [TABLE_DTYPE] / ident [uint8] of all
+    templates, template k at [table_begin[k], table_begin[k + 1]); ranges [m, 2] int32 (soff, send) of the accepted alignments, template
+    k's at [range_begin[k], range_begin[k + 1]).  The ident bytes are taken as given.  -> the plan dict of cns_accept_templates_plan"""
+    table = np.ascontiguousarray(table, dtype=TABLE_DTYPE)
+    ident = np.ascontiguousarray(ident, dtype=np.uint8)
+    tbeg = np.ascontiguousarray(table_begin, dtype=np.int64)
+    rng = np.ascontiguousarray(ranges, dtype=np.int32).reshape(-1, 2)
+    rbeg = np.ascontiguousarray(range_begin, dtype=np.int64)
+    assert len(tbeg) == len(rbeg) >= 1 and len(table) == len(ident) == tbeg[-1] and len(rng) == rbeg[-1]
+    seg, segb, win, er, erb = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    nwin = C.c_int64()
+    _chk(lib().mhip_debug_cns_plan(ctx.h, table.ctypes.data, ident.ctypes.data, tbeg.ctypes.data, len(tbeg) - 1, rng.ctypes.data, rbeg.ctypes.data, int(tech),
+                                   int(min_cov), int(min_size), C.byref(seg), C.byref(segb), C.byref(win), C.byref(nwin), C.byref(er), C.byref(erb)))
+    return _cns_plan_out(seg, segb, win, nwin, er, erb, len(tbeg) - 1)
 
 
 COMM_ID_BYTES = 128
