@@ -414,7 +414,8 @@ int  mhip_debug_cns_table(mhip_ctx* ctx, const char* buf, int64_t bytes, const i
  * the table is built on the device whether or not MHIP_CNS_WANT_TABLE is set, but it is copied to the host only with that bit; with
  * MHIP_CNS_WANT_PLAN alone neither strings nor tables cross the PCIe link.  Without MHIP_CNS_WANT_PLAN the six plan outputs come back
  * NULL / 0 (their pointers may be NULL then) and min_cov / min_size are not looked at.  All buffers are released with mhip_cns_free.
- * Retrieving the windows' substrings, the POA and the output of the corrected reads stay with the caller. */
+ * Retrieving the windows' substrings: mhip_cns_accept_templates_pieces below.  The POA and the output of the corrected reads stay with
+ * the caller. */
 typedef struct { int32_t template_index, beg, end, n_anchors; int64_t win_begin, win_end; } mhip_cns_segment;
 typedef struct { int32_t sb, se, cov, segment; } mhip_cns_window;       /* segment: index into out_segments */
 #define MHIP_CNS_WANT_PLAN 4
@@ -433,6 +434,46 @@ int  mhip_debug_cns_plan(mhip_ctx* ctx, const mhip_cns_table_item* table, const 
                          const int32_t* ranges, const int64_t* range_begin, int tech, int min_cov, int min_size,
                          mhip_cns_segment** out_segments, int64_t** out_seg_begin, mhip_cns_window** out_windows, int64_t* out_n_windows,
                          int32_t** out_eranges, int64_t** out_erange_begin);
+/* ---- the POA windows' substrings (cns_pieces.hip).  For a listed window (sb, se) the reference's meap_cns_one_indel
+ * (mecat_correction.cpp:62-78) asks every accepted alignment of the template, in add order, for its part of the window:
+ * CnsAln::retrieve_aln_subseqs (reads_correction_aux.h:47-68), a cursor per alignment that only moves forward, and feeds each pair of
+ * substrings it gets to the graph with ag.addAln(qstr, tstr, sb_out - sb + 1).  A piece is one such answer as a descriptor: the
+ * substrings are columns [col, col + ncols) of qaln and saln of accepted record `aln`, and sb_out = max(soff, sb).
+ *   columns       column c >= 1 of an alignment has template position soff + the number of non-gap characters in saln[1 .. c]; column 0
+ *                 has position soff whatever it holds (the cursor starts there without looking at it).
+ *   a piece       runs from the first column at position max(soff, sb) to the first column at position se, gap columns in between
+ *                 included, gap columns behind the base at se not; it stops at the last column, aln_size - 1, where the alignment ends
+ *                 inside the window.
+ *   no piece      se <= soff, sb >= send, aln_size < 2, or the template's previous listed window took the cursor to the last column
+ *                 (it overlaps the alignment and its se lies on or behind the last column): an alignment whose last base is a window's
+ *                 sb gives a one-column piece only when the stretch in front of that window was not listed.
+ * mhip_cns_accept_templates_pieces is mhip_cns_accept_templates_plan with MHIP_CNS_WANT_PIECES allowed in `want`.  Window w of
+ * out_windows owns out_pieces[out_piece_begin[w] .. out_piece_begin[w + 1]), in ascending `aln` — the reference's add order;
+ * out_piece_begin has *out_n_windows + 1 entries ({0} when there is no window).  MHIP_CNS_WANT_PIECES needs MHIP_CNS_WANT_PLAN (refused
+ * without it); PLAN | PIECES alone copies neither strings nor tables to the host.  Without the PIECES bit the call is
+ * mhip_cns_accept_templates_plan (the two outputs come back NULL, their pointers may be NULL).  mhip_cns_accept_templates_plan and _ex
+ * keep refusing the bit.  The output is the same bytes on every run; release with mhip_cns_free.  The POA itself (AlnGraphBoost) and
+ * the output of the corrected reads stay with the caller. */
+typedef struct { int32_t aln, col, ncols, sb_out; } mhip_cns_piece;   /* aln: index into out_accepted */
+#define MHIP_CNS_WANT_PIECES 8
+int  mhip_cns_accept_templates_pieces(mhip_ctx* ctx, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin,
+                                      int num_templates, int tech, int min_align_size, double min_mapping_ratio, int num_threads, int want,
+                                      int min_cov, int min_size, mhip_cns_accepted** out_accepted, int64_t* out_count, char** out_strings,
+                                      int64_t* out_strings_bytes, int64_t* out_jobs, mhip_cns_table_item** out_table, uint8_t** out_ident,
+                                      int64_t** out_table_begin /* [num_templates + 1] */, mhip_cns_segment** out_segments,
+                                      int64_t** out_seg_begin /* [num_templates + 1] */, mhip_cns_window** out_windows, int64_t* out_n_windows,
+                                      int32_t** out_eranges, int64_t** out_erange_begin /* [num_templates + 1] */,
+                                      mhip_cns_piece** out_pieces, int64_t** out_piece_begin /* [*out_n_windows + 1] */);
+/* test hook: the same piece kernels on ONE template: n_pairs alignments as host strings in mhip_debug_push_gaps' layout (pair p: qaln at
+ * buf + off[p], len[p] characters + NUL, saln right behind it) with soff[p] / send[p], and n_windows listed windows windows[2 w] = sb,
+ * windows[2 w + 1] = se.  `aln` of a piece is the pair's number.  Refused before anything is launched: more than 100 pairs
+ * (MAX_CNS_OVLPS); len < 1; a pair outside the buffer; negative coordinates; a pair whose coordinates are not the ones add_aln would get
+ * from the m5 record — [soff, send) is the stretch of template bases the strings hold, so send - soff must equal the number of non-gap
+ * characters of saln[0 .. len) (for the usual saln[0] != '-': soff + 1 + the non-gap characters of saln[1 ..)); windows that are not
+ * sb < se, not ascending or not disjoint (se of one > sb of the next).  -> *out_pieces, *out_piece_begin [n_windows + 1] */
+int  mhip_debug_cns_pieces(mhip_ctx* ctx, const char* buf, int64_t bytes, const int64_t* off, const int32_t* len, const int32_t* soff,
+                           const int32_t* send, int n_pairs, const int32_t* windows, int n_windows, mhip_cns_piece** out_pieces,
+                           int64_t** out_piece_begin);
 /* mhip_cns_free does not return a string buffer to the system at once: the library keeps the LARGEST released one (gigabytes — about
  * 14 GB for a config-2-sized batch) and hands it out again to the next batch that fits, because first-touching fresh pages costs
  * more than the batch's GPU time.  The parked buffer belongs to the process, not to a context (mhip_ctx_destroy leaves it).  This call

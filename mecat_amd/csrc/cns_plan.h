@@ -6,6 +6,7 @@
 struct CnsPlanDev {
     const mhip_cns_segment* d_seg = nullptr;      // [nseg] final records (global template, segment and window numbers)
     const mhip_cns_window* d_win = nullptr;       // [nwin]
+    const long long* d_segb = nullptr;            // [nt + 1] seg_begin on the device (what cns_pieces.hip finds a template's windows with)
     const long long* d_bad = nullptr;             // nonzero once cns_plan_emit has run: it did not write the windows that were counted (NULL: nothing ran)
     long long nseg = 0, nwin = 0;
     double wait_s = 0;                            // host seconds spent in the wait for the counts

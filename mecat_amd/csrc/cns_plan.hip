@@ -277,7 +277,7 @@ int cns_plan_launch(mhip_ctx* c, int set, const uint32_t* d_table, const uint8_t
         LAUNCH(c, "cns_plan_emit", cns_plan_windows<true>, grid_e, 256, 0, d_table, d_ident, d_tb, t_index0, d_seg, d_segb + nt, seg_base, (int32_t*)nullptr, d_wb, win_base, d_win, d_tot + 2);
         HIPCHK(hipGetLastError());
     }
-    out->d_seg = d_seg; out->d_win = d_win; out->d_bad = d_tot + 2; out->nseg = nseg; out->nwin = nwin;
+    out->d_seg = d_seg; out->d_win = d_win; out->d_segb = d_segb; out->d_bad = d_tot + 2; out->nseg = nseg; out->nwin = nwin;
     return 0;
 }
 

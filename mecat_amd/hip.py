@@ -130,6 +130,8 @@ def lib():
                                                  C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(vp)]
     L.mhip_debug_cns_plan.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(vp),
                                       C.POINTER(vp)]
+    L.mhip_cns_accept_templates_pieces.argtypes = L.mhip_cns_accept_templates_plan.argtypes + [C.POINTER(vp), C.POINTER(vp)]
+    L.mhip_debug_cns_pieces.argtypes = [vp, vp, i64, vp, vp, vp, vp, i32, vp, i32, C.POINTER(vp), C.POINTER(vp)]
     L.mhip_cns_free.argtypes = [vp]
     L.mhip_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
     L.mhip_host_free.argtypes = [vp]
@@ -595,6 +597,57 @@ def debug_cns_plan(ctx, table, ident, table_begin, ranges, range_begin, tech, mi
     _chk(lib().mhip_debug_cns_plan(ctx.h, table.ctypes.data, ident.ctypes.data, tbeg.ctypes.data, len(tbeg) - 1, rng.ctypes.data, rbeg.ctypes.data, int(tech),
                                    int(min_cov), int(min_size), C.byref(seg), C.byref(segb), C.byref(win), C.byref(nwin), C.byref(er), C.byref(erb)))
     return _cns_plan_out(seg, segb, win, nwin, er, erb, len(tbeg) - 1)
+
+
+CNS_WANT_PIECES = 8
+PIECE_DTYPE = np.dtype([("aln", np.int32), ("col", np.int32), ("ncols", np.int32), ("sb_out", np.int32)])              # mhip_cns_piece
+assert PIECE_DTYPE.itemsize == 16
+
+
+def cns_accept_templates_pieces(ctx, vol, cands, tmpl_begin, tech, min_align_size, min_mapping_ratio, want, min_cov, min_size, threads=8):
+    """cns_accept_templates_plan with CNS_WANT_PIECES allowed in `want` (it needs CNS_WANT_PLAN): what the reference hands to the POA for
+    every listed window — CnsAln::retrieve_aln_subseqs of every accepted alignment of the template, in add order — as descriptors.  The
+    plan dict gets two more entries: pieces [PIECE_DTYPE] and piece_begin [windows + 1]; window w owns pieces[piece_begin[w]:
+    piece_begin[w + 1]], ascending `aln` (index into `accepted`).  A piece's substrings are qaln[col: col + ncols] and saln[col: col + ncols]
+    of that record; the reference feeds them to the graph with addAln(qstr, tstr, sb_out - sb + 1).  Without CNS_WANT_PIECES the result
+    is cns_accept_templates_plan's.  With CNS_WANT_PLAN | CNS_WANT_PIECES alone neither strings nor tables are copied from the device."""
+    cands = np.ascontiguousarray(cands)
+    tb = np.ascontiguousarray(tmpl_begin, dtype=np.int64)
+    acc, st, tab, idn, tbeg = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    seg, segb, win, er, erb, pc, pcb = (C.c_void_p() for _ in range(7))
+    na, sb, nj, nwin = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    _chk(lib().mhip_cns_accept_templates_pieces(ctx.h, vol.h, cands.ctypes.data, tb.ctypes.data, len(tb) - 1, tech, min_align_size, float(min_mapping_ratio), threads,
+                                                int(want), int(min_cov), int(min_size), C.byref(acc), C.byref(na), C.byref(st), C.byref(sb), C.byref(nj), C.byref(tab),
+                                                C.byref(idn), C.byref(tbeg), C.byref(seg), C.byref(segb), C.byref(win), C.byref(nwin), C.byref(er), C.byref(erb),
+                                                C.byref(pc), C.byref(pcb)))
+    a = _cns_take(acc, ACCEPTED_DTYPE, na.value)
+    s = _cns_buffer(st, sb.value)
+    begin = _cns_take(tbeg, np.int64, len(tb))
+    nw = int(begin[-1]) if len(begin) else 0
+    plan = _cns_plan_out(seg, segb, win, nwin, er, erb, len(tb) - 1) if int(want) & CNS_WANT_PLAN else None
+    if plan is not None and int(want) & CNS_WANT_PIECES:
+        plan["piece_begin"] = _cns_take(pcb, np.int64, int(nwin.value) + 1)
+        npc = int(plan["piece_begin"][-1]) if len(plan["piece_begin"]) else 0
+        plan["pieces"] = _cns_buffer(pc, npc * PIECE_DTYPE.itemsize).view(PIECE_DTYPE)
+    return a, s, nj.value, _cns_buffer(tab, 4 * nw).view(TABLE_DTYPE), _cns_buffer(idn, nw), begin, plan
+
+
+def debug_cns_pieces(ctx, buf, off, lens, soff, send, windows):
+    """test hook: the piece kernels on one template.  buf: uint8 buffer, pair p = qaln at off[p] (lens[p] characters + NUL), saln right
+    behind it, with soff[p] / send[p]; windows [k, 2] int32 (sb, se), ascending and disjoint.  -> (pieces [PIECE_DTYPE], piece_begin
+    [k + 1]); `aln` is the pair's number"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    soff = np.ascontiguousarray(soff, dtype=np.int32)
+    send = np.ascontiguousarray(send, dtype=np.int32)
+    win = np.ascontiguousarray(windows, dtype=np.int32).reshape(-1, 2)
+    assert len(off) == len(lens) == len(soff) == len(send)
+    pc, pcb = C.c_void_p(), C.c_void_p()
+    _chk(lib().mhip_debug_cns_pieces(ctx.h, buf.ctypes.data, len(buf), off.ctypes.data, lens.ctypes.data, soff.ctypes.data, send.ctypes.data, len(off), win.ctypes.data,
+                                     len(win), C.byref(pc), C.byref(pcb)))
+    piece_begin = _cns_take(pcb, np.int64, len(win) + 1)
+    return _cns_take(pc, PIECE_DTYPE, int(piece_begin[-1])), piece_begin
 
 
 COMM_ID_BYTES = 128
