@@ -124,7 +124,8 @@ __host__ __device__ __forceinline__ int sel_rid(const ReadSel& s, int i) {
 // bucket walk of a diagonal cell is not done.  counters[1] still counts every bucket hit (the H of SURVEY.md §8d).
 __global__ __launch_bounds__(SEED_BLOCK) void seed_probe(const uint32_t* __restrict__ pac, const mhip_offset_t* __restrict__ roffs,
                                                          ReadSel sel, int ib, const uint32_t* __restrict__ starts, SeedArrays A,
-                                                         unsigned long long* __restrict__ counters, const uint4* __restrict__ recs, int cut_step) {
+                                                         unsigned long long* __restrict__ counters, const uint4* __restrict__ recs, int cut_step,
+                                                         int tally) {
     __shared__ uint32_t wtot[SEED_WAVES];
     const int s = blockIdx.x;
     const int rid = sel_rid(sel, ib + (s >> 1));
@@ -175,9 +176,11 @@ __global__ __launch_bounds__(SEED_BLOCK) void seed_probe(const uint32_t* __restr
     }
     if (threadIdx.x == 0) {
         A.strand_hits_all[s] = run;
-        atomicAdd(&counters[0], (unsigned long long)K);
-        atomicAdd(&counters[1], (unsigned long long)run_all);
-        if (recs) atomicAdd(&counters[15], (unsigned long long)run);      // debug slot 15: bucket hits walked with the cuts on
+        if (tally) {                // (0: seed_strand has counted these lookups already and only the km_* arrays are wanted, see seed_batch)
+            atomicAdd(&counters[0], (unsigned long long)K);
+            atomicAdd(&counters[1], (unsigned long long)run_all);
+            if (recs) atomicAdd(&counters[15], (unsigned long long)run);      // debug slot 15: bucket hits walked with the cuts on
+        }
     }
 }
 
@@ -846,60 +849,135 @@ struct FsLds {
     uint32_t occ[REL_WORDS];
     uint32_t rel[REL_WORDS];
     uint16_t base_ci[REL_WORDS];
-    uint32_t sq_id[FS_SEGCAP];                           // segment table in slot-major order q
+    uint32_t sq_id[FS_SEGCAP];                           // segment table in slot-major order q; until phase A: bucket start of every k-mer
     uint16_t sq_st[FS_SEGCAP + 2];                       // first recorded event of the segment; [nseg] = nrec
-    uint16_t sq_score[FS_SEGCAP];                        // live score | FS_OVF16
+    uint16_t sq_score[FS_SEGCAP];                        // live score | FS_OVF16; until phase B: bucket size of every k-mer
     uint16_t gate[FS_GATECAP];
     uint32_t qpos[FS_WAVES][128];                        // walk 2: kept hits waiting for a full wave (position, km)
     uint16_t qkm[FS_WAVES][128];
     uint32_t wtot[FS_WAVES];
-    uint32_t misc[8];                                    // 0 big count, 1 overflow count, 2 gated count, 3 fail flag, 4/5 carry, 6 hb lo, 7 hb hi
+    unsigned long long red[FS_WAVES];                    // fs_block_sum2
+    unsigned long long tally[3];                         // the workgroup's share of counters[0], [1], [15] (thread 0)
+    uint32_t misc[12];                                   // 0 big count, 1 overflow count, 2 gated count, 3 fail flag, 4/5 carry, 6 hb lo, 7 hb hi,
+                                                         // 8 / 9 strands taken from the cursor (not cleared between strands)
 };
 static_assert(sizeof(FsLds) <= 160 * 1024 - 512, "one workgroup per CU");
 
-struct FusedCtl { unsigned long long alloc; unsigned int n_fallback; unsigned int pad; unsigned long long prof[32]; };
+struct FusedCtl { unsigned long long alloc; unsigned int n_fallback; unsigned int next /* strand cursor */; unsigned long long prof[32]; };
 #ifdef FS_PROF
-#define FS_MARK(i) do { __syncthreads(); if (threadIdx.x == 0) { const unsigned long long t_ = wall_clock64(); atomicAdd(&ctl->prof[(i) + 16 * (blockIdx.x & 1)], t_ - t_prev); t_prev = t_; } } while (0)
+#define FS_MARK(i) do { __syncthreads(); if (threadIdx.x == 0) { const unsigned long long t_ = wall_clock64(); atomicAdd(&ctl->prof[(i) + 16 * (s & 1)], t_ - t_prev); t_prev = t_; } } while (0)
 #else
 #define FS_MARK(i) do { } while (0)
 #endif
 
-// block-wide exclusive scan, FS_THREADS threads
-__device__ __forceinline__ uint32_t fs_excl_scan(uint32_t v, uint32_t* wtot, uint32_t* total) {
+// block-wide exclusive scan, FS_THREADS threads.  The thread index is an argument (as in fs_walk and fs_block_sum2): seed_strand hands in
+// a copy the compiler cannot see through, so that the lane masks and shuffle addresses are made where they are used and not once in
+// front of its strand loop, where they would occupy registers through every phase.
+__device__ __forceinline__ uint32_t fs_excl_scan(const int tid, uint32_t v, uint32_t* wtot, uint32_t* total) {
+    const int lane = tid & 63, wave = tid >> 6;
     uint32_t incl = v;
     for (int o = 1; o < 64; o <<= 1) {
-        uint32_t n = __shfl_up(incl, o);
-        if (lane_id() >= o) incl += n;
+        const uint32_t n = (uint32_t)__builtin_amdgcn_ds_bpermute(((lane - o) & 63) << 2, (int)incl);
+        if (lane >= o) incl += n;
     }
     __syncthreads();
-    if (lane_id() == 63) wtot[threadIdx.x >> 6] = incl;
+    if (lane == 63) wtot[wave] = incl;
     __syncthreads();
     uint32_t base = 0, tot = 0;
 #pragma unroll
     for (int w = 0; w < FS_WAVES; ++w) {
         const uint32_t x = wtot[w];
-        if (w < (int)(threadIdx.x >> 6)) base += x;
+        if (w < wave) base += x;
         tot += x;
     }
     *total = tot;
     return base + incl - v;
 }
 
+// block-wide sums of two values per thread, FS_THREADS threads (a barrier inside: what was written to LDS before the call is visible after it)
+__device__ __forceinline__ void fs_block_sum2(const int tid, uint32_t a, uint32_t b, unsigned long long* red /*[FS_WAVES]*/, uint32_t* sa, uint32_t* sb) {
+    const int lane = tid & 63;
+    for (int o = 32; o > 0; o >>= 1) {
+        a += (uint32_t)__builtin_amdgcn_ds_bpermute((lane ^ o) << 2, (int)a);
+        b += (uint32_t)__builtin_amdgcn_ds_bpermute((lane ^ o) << 2, (int)b);
+    }
+    const unsigned long long v = (unsigned long long)a | ((unsigned long long)b << 32);      // (each wave's sums are below 2^32)
+    if (lane == 0) red[tid >> 6] = v;
+    __syncthreads();
+    unsigned long long t = 0;
+#pragma unroll
+    for (int w = 0; w < FS_WAVES; ++w) t += red[w];
+    *sa = (uint32_t)t;
+    *sb = (uint32_t)(t >> 32);
+}
+
+// What seed_probe computes per query k-mer, in the two dependent steps seed_strand issues apart: the two packed words that hold the
+// k-mer, then the bucket's record (the cut record of a diagonal cell, or starts[id] and starts[id + 1]), kept raw until it is needed.
+struct FsStrand { int rid, off, len, K, cut_byte; bool rev; };
+__device__ __forceinline__ FsStrand fs_strand(const mhip_offset_t* __restrict__ roffs, const ReadSel& sel, int ib, int s, bool cuts, int cut_step) {
+    FsStrand d;
+    d.rid = sel_rid(sel, ib + (s >> 1));
+    d.off = roffs[d.rid].offset;
+    d.len = roffs[d.rid].size;
+    d.K = kmers_of(d.len);
+    d.rev = s & 1;
+    d.cut_byte = 7;                 // byte of the record's y:z that holds the bucket length for this read (seed_probe)
+    if (cuts) {
+        const long long need = (long long)d.off + d.len + 1 + 5 * ZV;
+        const long long t = (need + cut_step - 1) / cut_step;
+        if (t <= 7) d.cut_byte = (int)t - 1;
+    }
+    return d;
+}
+__device__ __forceinline__ int64_t fs_kmer_at(const FsStrand& d, int km) {
+    return !d.rev ? (int64_t)d.off + (int64_t)km * BC : (int64_t)d.off + d.len - MHIP_KMER_SIZE - (int64_t)km * BC;
+}
+__device__ __forceinline__ void fs_hdr_words(const uint32_t* __restrict__ pac, const FsStrand& d, int km, uint32_t (&w)[2]) {
+    const int64_t i = fs_kmer_at(d, km) >> 4;
+    w[0] = pac[i];
+    w[1] = pac[i + 1];
+}
+__device__ __forceinline__ void fs_hdr_record(const uint32_t* __restrict__ starts, const uint4* __restrict__ recs, const FsStrand& d, int km,
+                                              const uint32_t (&w)[2], uint32_t (&r)[3]) {
+    const uint64_t W = ((uint64_t)__builtin_bswap32(w[0]) << 32) | __builtin_bswap32(w[1]);      // pac_kmer
+    uint32_t id = (uint32_t)(W >> (64 - 26 - (int)((fs_kmer_at(d, km) & 15) << 1))) & KMER_MASK;
+    if (d.rev) id = kmer_revcomp(id);
+    if (recs) {
+        const uint4 v = recs[id];
+        r[0] = v.x; r[1] = v.y; r[2] = v.z;
+    } else {
+        r[0] = starts[id]; r[1] = starts[id + 1];      // (r[2] is left alone: nothing here may touch a loaded value, see seed_strand)
+    }
+}
+__device__ __forceinline__ void fs_hdr_decode(bool cuts, const FsStrand& d, const uint32_t (&r)[3], uint32_t* bs, uint32_t* cnt, uint32_t* all) {
+    *bs = r[0];
+    if (cuts) {
+        // byte cut_byte of y:z, word by word (a 64-bit y:z here would make the compiler keep the raw records as one 64-bit value and
+        // combine them where they are loaded: a wait behind the prefetch loads)
+        *all = r[2] >> 24;
+        *cnt = ((d.cut_byte < 4 ? r[1] : r[2]) >> (8 * (d.cut_byte & 3))) & 0xFFu;
+    } else {
+        *all = *cnt = r[1] - r[0];
+    }
+}
+
 // pipelined walk over the buckets of a strand; f(km, value) per hit.  LPB lanes per bucket, Q buckets per group and stage, D stages
 // of bucket data in flight plus one stage of bucket headers (start, size) ahead of them.  The first NP * LPB entries of a bucket are
 // loaded by the pipeline (NP pieces of LPB); a longer bucket reads the rest when it is consumed.
-template <int LPB, int NP, int Q, int D, bool UNIFORM, typename T, typename F>
-__device__ __forceinline__ void fs_walk(const uint32_t* __restrict__ kbs, const uint32_t* __restrict__ kcn, const T* __restrict__ arr, const int K, F f) {
+// The headers come from `kbs` / `kcn`: the km_* arrays in HBM (seed_filter_wide) or a strand's copy in LDS (seed_strand, 16-bit counts).
+template <int LPB, int NP, int Q, int D, bool UNIFORM, typename T, typename C, typename F>
+__device__ __forceinline__ void fs_walk(const int tid, const uint32_t* __restrict__ kbs, const C* __restrict__ kcn, const T* __restrict__ arr,
+                                        const int K, F f) {
     constexpr int G = FS_THREADS / LPB, STEP = Q * G;
-    const int g = threadIdx.x / LPB;
-    const uint32_t sub = threadIdx.x % LPB;
+    const int g = tid / LPB;
+    const uint32_t sub = (uint32_t)tid % LPB;
     uint32_t hb[Q], hc[Q];                          // headers of stage D (no data requested yet)
     uint32_t sb[D][Q], sc[D][Q], sd[D][Q][NP];      // stages 0 .. D-1: header and data
 #define FS_HDR(BASE, BS, CN)                                                      \
     _Pragma("unroll") for (int q = 0; q < Q; ++q) {                               \
         const int km_ = (BASE) + q * G + g;                                       \
         BS[q] = km_ < K ? kbs[km_] : 0u;                                          \
-        CN[q] = km_ < K ? kcn[km_] : 0u;                                          \
+        CN[q] = km_ < K ? (uint32_t)kcn[km_] : 0u;                                \
     }
 #define FS_DAT(BS, CN, DD)                                                        \
     _Pragma("unroll") for (int q = 0; q < Q; ++q)                                 \
@@ -967,7 +1045,7 @@ __device__ __forceinline__ void fs_walk(const uint32_t* __restrict__ kbs, const 
 
 // ascending sort of p[0 .. n) (LDS, n <= 64 NQ) by one wave: bitonic network, element q * 64 + lane in register v[q]
 template <int NQ>
-__device__ __noinline__ void fs_bitonic(uint32_t* p, const uint32_t n, const int lane) {
+__device__ __forceinline__ void fs_bitonic(uint32_t* p, const uint32_t n, const int lane) {
     uint32_t v[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) { const uint32_t idx = q * 64 + lane; v[q] = idx < n ? p[idx] : 0xFFFFFFFFu; }
@@ -989,7 +1067,7 @@ __device__ __noinline__ void fs_bitonic(uint32_t* p, const uint32_t n, const int
             } else {
 #pragma unroll
                 for (int q = 0; q < NQ; ++q) {
-                    const uint32_t o = (uint32_t)__shfl_xor((int)v[q], j);
+                    const uint32_t o = (uint32_t)__builtin_amdgcn_ds_bpermute((lane ^ j) << 2, (int)v[q]);
                     const bool asc = (((q * 64 + lane) & k) == 0), lower = (lane & j) == 0;
                     v[q] = (asc == lower) ? min(v[q], o) : max(v[q], o);
                 }
@@ -1066,7 +1144,7 @@ __global__ __launch_bounds__(FS_THREADS) void seed_filter_wide(const mhip_offset
     // counted apart, and the read's own segments are relevant whatever the counters say.
     const bool own = same_volume && !(s & 1);
     const uint32_t own_off = (uint32_t)roffs[rid].offset;
-    fs_walk<WF_LPB, WF_NP, WF_Q, WF_D, false>(A.km_bstart + kb, A.km_cnt + kb, offsets, K, [&](int km, uint32_t pos) {
+    fs_walk<WF_LPB, WF_NP, WF_Q, WF_D, false>(tid, A.km_bstart + kb, A.km_cnt + kb, offsets, K, [&](int km, uint32_t pos) {
 #if defined(WF_KNOCK) && WF_KNOCK == 1
         if (pos == 0xfffffff1u) atomicAdd(&s_self, 1u);      // timing experiment: the gather alone (results are wrong)
         return;
@@ -1164,7 +1242,7 @@ __global__ __launch_bounds__(FS_THREADS) void seed_filter_wide(const mhip_offset
         }
     }
     uint32_t kept;
-    (void)fs_excl_scan(mine, wtot, &kept);
+    (void)fs_excl_scan(tid, mine, wtot, &kept);
     A.rel_bits[(size_t)s * REL_WORDS + tid] = rel[tid];
     if (tid == 0) {
         const uint32_t room = min(Hall, kept + s_self + 16u * s_wraps);
@@ -1175,37 +1253,118 @@ __global__ __launch_bounds__(FS_THREADS) void seed_filter_wide(const mhip_offset
     WF_MARK(3);
 }
 
-__global__ __launch_bounds__(FS_THREADS) void seed_strand(const mhip_offset_t* __restrict__ roffs, ReadSel sel, int ib,
-                                                          const uint16_t* __restrict__ slots, const int32_t* __restrict__ offsets, SeedArrays A,
-                                                          int gate, int hi_bits, int min_kmer_match, double cutoff, unsigned long long cap,
-                                                          FusedCtl* __restrict__ ctl, unsigned long long* __restrict__ counters, RefReads R) {
+// seed_strand is persistent: one workgroup per CU, each taking strands from a cursor (ctl->next) one ahead of the strand it works on.
+// The bucket headers of a strand (what seed_probe computes: start and size of the bucket of every query k-mer) are fetched by the
+// workgroup itself and live in LDS for both walks, in the place of sq_id / sq_score, which the build writes only after walk 2.  Those
+// of the NEXT strand are requested while the memory pipeline has nothing else to do: the packed words of the read in front of walk 2,
+// the records behind it; the raw records (two per thread: K <= 2 * FS_THREADS) wait in registers through the LDS phases of this
+// strand and are decoded at the top of the next.  Longer strands, the first strand of a workgroup and a strand behind one that left
+// early fetch what is missing there, unhidden.  A strand with more than FS_SEGCAP k-mers is left to the kernel chain.
+// A.km_bstart != nullptr (MECAT_SEED_FUSED_PROBE=0): seed_probe has run, the headers are copied from its arrays and nothing is tallied here.
+// Registers.  A 1 024-thread workgroup may use 128 VGPRs per thread, and the kernel stands at that limit: 128 VGPRs, no scratch, 4 waves
+// per SIMD (79 VGPRs before the strand loop: what LLVM hoists out of that loop — constants, lane masks — stays live through every phase).
+// Several things here exist only to keep it out of scratch: the opaque thread index per strand, FS_UNI, the thread index handed to
+// fs_walk / fs_excl_scan / fs_block_sum2, ds_bpermute with an explicit lane in place of __shfl_*, fs_bitonic inlined, the tallies in
+// LDS.  After any edit to this kernel, and after a compiler change, check
+//   hipcc --offload-arch=gfx950 <HIPFLAGS of the Makefile> -Rpass-analysis=kernel-resource-usage -c mecat_amd/csrc/seed.hip
+// for seed_strand: `ScratchSize [bytes/lane]: 0`, `VGPRs Spill: 0`, `Occupancy [waves/SIMD]: 4` (profiles/seed_headers.md has the record).
+#define FS_UNI(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))
+__global__ __launch_bounds__(FS_THREADS) void seed_strand(const uint32_t* __restrict__ pac, const mhip_offset_t* __restrict__ roffs, ReadSel sel,
+                                                          int ib, int ns, const uint32_t* __restrict__ starts, const uint4* __restrict__ recs,
+                                                          int cut_step, const uint16_t* __restrict__ slots, const int32_t* __restrict__ offsets,
+                                                          SeedArrays A, int gate, int hi_bits, int min_kmer_match, double cutoff,
+                                                          unsigned long long cap, FusedCtl* __restrict__ ctl,
+                                                          unsigned long long* __restrict__ counters, RefReads R) {
     __shared__ FsLds L;
-    const int s = blockIdx.x;
-    const int tid = threadIdx.x, lane = lane_id(), wv = threadIdx.x >> 6;
-    const int rid = sel_rid(sel, ib + (s >> 1));
-    const int rlen = roffs[rid].size;
-    const int K = kmers_of(rlen);
-    const uint32_t kb = A.km_base[s];
-    const uint32_t Hall = A.strand_hits_all[s];
-    const uint32_t* __restrict__ kbs = A.km_bstart + kb;
-    const uint32_t* __restrict__ kcn = A.km_cnt + kb;
+    const int tid0 = threadIdx.x;
+    const bool probed = A.km_bstart != nullptr;
+    const bool cuts = recs != nullptr;
+    uint32_t* const hbs = L.sq_id;                       // the strand's bucket headers, [K] (K <= FS_SEGCAP)
+    uint16_t* const hcn = L.sq_score;
+    constexpr int PF = 2;                                // prefetched records per thread
+    uint32_t pw[PF][2], pr[PF][3];                       // the next strand's packed words / raw records of k-mers tid, tid + FS_THREADS
+#pragma unroll
+    for (int j = 0; j < PF; ++j) { pw[j][0] = pw[j][1] = 0; pr[j][0] = pr[j][1] = pr[j][2] = 0; }
+    int pf = -1;                                         // the strand pr[] belongs to
+    if (tid0 == 0) { L.tally[0] = L.tally[1] = L.tally[2] = 0; L.misc[8] = atomicAdd(&ctl->next, 1u); L.misc[9] = atomicAdd(&ctl->next, 1u); }
+    __syncthreads();
+    // (block-uniform values that decide a `continue` are made scalar: the strand loop then has uniform branches only)
+    int s = (int)min(FS_UNI(L.misc[8]), (uint32_t)ns), sn = (int)min(FS_UNI(L.misc[9]), (uint32_t)ns), s2 = ns;
+    for (; s < ns; s = sn, sn = s2) {
+    __syncthreads();                                     // the strand before is through with the LDS (and everybody has read misc[8])
+    // (the thread index is made opaque per strand: what is derived from it — addresses, masks — would otherwise be hoisted out of the strand
+    // loop and held in registers across all phases, which costs the kernel its 4 waves per SIMD)
+    int tid = tid0;
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const FsStrand d = fs_strand(roffs, sel, ib, s, cuts, cut_step);
+    const int rid = d.rid, rlen = d.len, K = d.K;
     auto fail = [&]() {                     // called by all threads together
         if (tid == 0) { A.fused[s] = 0; atomicAdd(&ctl->n_fallback, 1u); atomicAdd(&counters[14], 1ull); }      // debug slot 14: strands left to the kernel chain
     };
-    if (Hall == 0) {
-        if (tid == 0) { A.fused[s] = 1; A.strand_hits[s] = 0; A.hit_base[s] = 0; A.nseg[s] = 0; A.nrec[s] = 0; A.ngated[s] = 0; }
-        return;
-    }
-    if (Hall >= 65536u || K > 32767) { fail(); return; }        // a 16-bit counter could wrap; km has 15 bits in the payload
-
     unsigned long long t_prev = wall_clock64(); (void)t_prev;
-    // ---- walk 1: hits per table slot
     for (int i = tid; i < FLT_M / 2; i += FS_THREADS) L.x.cnt32[i] = 0;
     for (int i = tid; i < REL_WORDS; i += FS_THREADS) L.rel[i] = 0u;
     if (tid < 8) L.misc[tid] = 0;
-    __syncthreads();
+    if (tid == 0) L.misc[8] = atomicAdd(&ctl->next, 1u);           // the strand after the next
+    // ---- bucket headers -> LDS; hits of the strand
+    uint32_t Hall, run_all;
+    {
+        const bool room = K <= FS_SEGCAP;                // (a longer strand fails below: only its sums are wanted)
+        uint32_t hc = 0, ha = 0;
+        if (probed) {
+            const uint32_t kb = A.km_base[s];
+            for (int km = tid; km < K; km += FS_THREADS) {
+                const uint32_t bs = A.km_bstart[kb + km], cn = A.km_cnt[kb + km];
+                hc += cn;
+                if (room) { hbs[km] = bs; hcn[km] = (uint16_t)cn; }
+            }
+        } else {
+            auto take = [&](int km, const uint32_t (&r)[3]) {
+                uint32_t bs, cn, al;
+                fs_hdr_decode(cuts, d, r, &bs, &cn, &al);
+                hc += cn;
+                ha += al;
+                if (room) { hbs[km] = bs; hcn[km] = (uint16_t)cn; }
+            };
+            if (pf != s) {                               // nothing prefetched for this strand: its first records now
+#pragma unroll
+                for (int j = 0; j < PF; ++j)
+                    if (tid + j * FS_THREADS < K) fs_hdr_words(pac, d, tid + j * FS_THREADS, pw[j]);
+#pragma unroll
+                for (int j = 0; j < PF; ++j)
+                    if (tid + j * FS_THREADS < K) fs_hdr_record(starts, recs, d, tid + j * FS_THREADS, pw[j], pr[j]);
+            }
+            // (the first use of the raw records, pinned here: without it the compiler moves the word combine of fs_hdr_decode up to the
+            // loads behind walk 2, and with it the wait for them)
+#pragma unroll
+            for (int j = 0; j < PF; ++j) asm volatile("" : "+v"(pr[j][0]), "+v"(pr[j][1]), "+v"(pr[j][2]));
+#pragma unroll
+            for (int j = 0; j < PF; ++j)
+                if (tid + j * FS_THREADS < K) take(tid + j * FS_THREADS, pr[j]);
+            for (int km = tid + PF * FS_THREADS; km < K; km += FS_THREADS) {
+                uint32_t w[2], r[3] = {0, 0, 0};
+                fs_hdr_words(pac, d, km, w);
+                fs_hdr_record(starts, recs, d, km, w, r);
+                take(km, r);
+            }
+        }
+        fs_block_sum2(tid, hc, ha, L.red, &Hall, &run_all);   // (its barrier: the cleared tables, the headers and misc[8] are visible)
+        Hall = FS_UNI(Hall);
+        run_all = FS_UNI(run_all);
+        s2 = (int)min(FS_UNI(L.misc[8]), (uint32_t)ns);
+        if (!probed && tid == 0) { L.tally[0] += (unsigned long long)K; L.tally[1] += run_all; L.tally[2] += Hall; A.strand_hits_all[s] = Hall; }
+    }
+    if (Hall == 0) {
+        if (tid == 0) { A.fused[s] = 1; A.strand_hits[s] = 0; A.hit_base[s] = 0; A.nseg[s] = 0; A.nrec[s] = 0; A.ngated[s] = 0; }
+        continue;
+    }
+    // a 16-bit counter could wrap; km has 15 bits in the payload; the headers have FS_SEGCAP places
+    if (Hall >= 65536u || K > 32767 || K > FS_SEGCAP) { fail(); continue; }
+
+    // ---- walk 1: hits per table slot
     FS_MARK(0);
-    fs_walk<FS_LPB1, FS_NP1, FS_Q1, FS_D1, false>(kbs, kcn, slots, K, [&](int, uint32_t e) { atomicAdd(&L.x.cnt32[e >> 1], 1u << ((e & 1u) * 16u)); });
+    fs_walk<FS_LPB1, FS_NP1, FS_Q1, FS_D1, false>(tid, hbs, hcn, slots, K, [&](int, uint32_t e) { atomicAdd(&L.x.cnt32[e >> 1], 1u << ((e & 1u) * 16u)); });
     __syncthreads();
     FS_MARK(1);
 
@@ -1257,10 +1416,10 @@ __global__ __launch_bounds__(FS_THREADS) void seed_strand(const mhip_offset_t* _
         }
         // one scan for both prefixes: hits in the low half (Hall < 2^16), occupied slots in the high half (<= 2^15)
         uint32_t both;
-        const uint32_t exb = fs_excl_scan(mine | ((uint32_t)__popc(occ) << 16), L.wtot, &both);
+        const uint32_t exb = fs_excl_scan(tid, mine | ((uint32_t)__popc(occ) << 16), L.wtot, &both);
         const uint32_t ex = exb & 0xFFFFu, cx = exb >> 16;
-        kept = both & 0xFFFFu;
-        if (kept > FS_CAP) { fail(); return; }
+        kept = FS_UNI(both) & 0xFFFFu;
+        if (kept > FS_CAP) { fail(); continue; }
         L.occ[tid] = occ;
         L.base_ci[tid] = (uint16_t)cx;
         uint16_t* cur16 = (uint16_t*)L.y.cur32;
@@ -1274,11 +1433,11 @@ __global__ __launch_bounds__(FS_THREADS) void seed_strand(const mhip_offset_t* _
         }
         if (toolong) L.misc[3] = 1;
         __syncthreads();
-        if (L.misc[3]) { fail(); return; }
+        if (FS_UNI(L.misc[3])) { fail(); continue; }
     }
     if (kept == 0) {
         if (tid == 0) { A.fused[s] = 1; A.strand_hits[s] = 0; A.hit_base[s] = 0; A.nseg[s] = 0; A.nrec[s] = 0; A.ngated[s] = 0; }
-        return;
+        continue;
     }
     // room in the shared output arrays
     if (tid == 0) {
@@ -1288,10 +1447,19 @@ __global__ __launch_bounds__(FS_THREADS) void seed_strand(const mhip_offset_t* _
         L.misc[7] = (uint32_t)(hb0 >> 32);
     }
     __syncthreads();                                      // also: cnt32 is dead from here, the payload arrays take its place
-    if (L.misc[3]) { fail(); return; }
+    if (FS_UNI(L.misc[3])) { fail(); continue; }
     const uint64_t hb = ((uint64_t)L.misc[7] << 32) | L.misc[6];
 
     FS_MARK(3);
+    // ---- the next strand's headers, step 1: the packed words of its k-mers (they arrive during walk 2)
+    const bool ahead = !probed && sn < ns;
+    FsStrand dn = d;
+    if (ahead) {
+        dn = fs_strand(roffs, sel, ib, sn, cuts, cut_step);
+#pragma unroll
+        for (int j = 0; j < PF; ++j)
+            if (tid + j * FS_THREADS < dn.K) fs_hdr_words(pac, dn, tid + j * FS_THREADS, pw[j]);
+    }
     // ---- walk 2: kept hits into their slot's region
     // A kept hit is rare (one in nine): the wave parks kept hits in its queue and places 64 of them at a time, so that the
     // cursor arithmetic runs with every lane busy.
@@ -1308,7 +1476,7 @@ __global__ __launch_bounds__(FS_THREADS) void seed_strand(const mhip_offset_t* _
             L.x.e.pay[p] = ((seg >> FLT_BITS) << 26) | (km << 11) | off;
             L.x.e.eslot[p] = (uint16_t)e;
         };
-        fs_walk<FS_LPB2, FS_NP2, FS_Q2, FS_D2, true>(kbs, kcn, offsets, K, [&](int km, uint32_t pos, bool valid) {
+        fs_walk<FS_LPB2, FS_NP2, FS_Q2, FS_D2, true>(tid, hbs, hcn, offsets, K, [&](int km, uint32_t pos, bool valid) {
             const uint32_t seg = pos / (uint32_t)ZV;
             const uint32_t e = seg & (FLT_M - 1);
             const uint32_t oc = valid ? L.occ[e >> 5] : 0u;
@@ -1325,6 +1493,15 @@ __global__ __launch_bounds__(FS_THREADS) void seed_strand(const mhip_offset_t* _
             }
         });
         if ((uint32_t)lane < qn) place((uint32_t)lane);
+    }
+    // ---- the next strand's headers, step 2: the records.  The memory pipeline is idle from here to the output of this strand, and
+    // nothing waits for these loads before the top of the next iteration (unless this strand's own few loads and stores do: vmcnt
+    // counts in order, and by then the records have long arrived).
+    if (ahead) {
+#pragma unroll
+        for (int j = 0; j < PF; ++j)
+            if (tid + j * FS_THREADS < dn.K) fs_hdr_record(starts, recs, dn, tid + j * FS_THREADS, pw[j], pr[j]);
+        pf = sn;
     }
     __syncthreads();
     FS_MARK(4);
@@ -1394,11 +1571,12 @@ __global__ __launch_bounds__(FS_THREADS) void seed_strand(const mhip_offset_t* _
             if (in) { ppay = pv[c]; psl = sv[c]; }
         }
         uint32_t both;
-        const uint32_t ex = fs_excl_scan((uint32_t)__popc(rm) | ((uint32_t)__popc(hm) << 16), L.wtot, &both);     // its barriers come after all the reads
+        const uint32_t ex = fs_excl_scan(tid, (uint32_t)__popc(rm) | ((uint32_t)__popc(hm) << 16), L.wtot, &both);     // its barriers come after all the reads
         uint32_t rpos = ex & 0xFFFFu, spos = ex >> 16;
+        both = FS_UNI(both);
         nrec = both & 0xFFFFu;
         nseg = both >> 16;
-        if (nseg > FS_SEGCAP) { fail(); return; }
+        if (nseg > FS_SEGCAP) { fail(); continue; }
 #pragma unroll
         for (int c = 0; c < CHMAX; ++c) {
             if ((rm >> c) & 1u) {
@@ -1432,7 +1610,7 @@ __global__ __launch_bounds__(FS_THREADS) void seed_strand(const mhip_offset_t* _
             static_assert(FS_WAVES == 16, "16 waves");
             const uint32_t v = L.x.e.hist[w][bin];
             uint32_t all;
-            const uint32_t ex = fs_excl_scan(v, L.wtot, &all);
+            const uint32_t ex = fs_excl_scan(tid, v, L.wtot, &all);
             L.x.e.hist[w][bin] = ex;
         }
         __syncthreads();
@@ -1467,7 +1645,7 @@ __global__ __launch_bounds__(FS_THREADS) void seed_strand(const mhip_offset_t* _
         }
     }
     __syncthreads();
-    if (L.misc[1] > FS_BIGCAP) { fail(); return; }
+    if (FS_UNI(L.misc[1]) > FS_BIGCAP) { fail(); continue; }
     // ---- phase C: insert_loc replay, one wave per overflowed segment (final lists and running scores go to HBM)
     {
         const uint32_t novf = L.misc[1];
@@ -1511,8 +1689,8 @@ __global__ __launch_bounds__(FS_THREADS) void seed_strand(const mhip_offset_t* _
         }
     }
     __syncthreads();
-    const uint32_t ng = L.misc[2];
-    if (ng > FS_GATECAP) { fail(); return; }
+    const uint32_t ng = FS_UNI(L.misc[2]);
+    if (ng > FS_GATECAP) { fail(); continue; }
     FS_MARK(9);
     // ---- phase E + output
     for (uint32_t a = tid; a < ng; a += FS_THREADS) {
@@ -1539,8 +1717,15 @@ __global__ __launch_bounds__(FS_THREADS) void seed_strand(const mhip_offset_t* _
         A.nrec[s] = nrec;
         A.ngated[s] = ng;
     }
+    }       // strands
+    if (!probed && tid0 == 0) {              // what seed_probe tallies, once per workgroup
+        atomicAdd(&counters[0], L.tally[0]);
+        atomicAdd(&counters[1], L.tally[1]);
+        if (cuts) atomicAdd(&counters[15], L.tally[2]);      // debug slot 15: bucket hits walked with the cuts on
+    }
 }
 
+#undef FS_UNI
 // ------------------------------------------------------------------------------------------------ candidates
 struct CandLds {
     int t_loc[2 * SM + 10];
@@ -1894,6 +2079,7 @@ static bool fused_enabled(const mhip_params* P);
 static bool wide_filter_enabled(const mhip_params* P);
 static bool predrop_enabled();
 static bool cuts_enabled(const mhip_params* P);
+static bool fused_probe_enabled();
 
 // the reads with local index in [ib, ie) of the selection
 static int seed_batch(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, const ReadSel sel,
@@ -1912,8 +2098,6 @@ static int seed_batch(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref
     memset(&A, 0, sizeof(A));
     uint32_t* d_kmb;
     if (c->scratch("sd_kmbase", sizeof(uint32_t) * (size_t)ns, (void**)&d_kmb)) return -1;
-    if (c->scratch("sd_kmbstart", sizeof(uint32_t) * (size_t)(sumK + 1), (void**)&A.km_bstart)) return -1;
-    if (c->scratch("sd_kmcnt", sizeof(uint32_t) * (size_t)(sumK + 1), (void**)&A.km_cnt)) return -1;
     if (c->scratch("sd_hitsall", sizeof(uint32_t) * (size_t)ns, (void**)&A.strand_hits_all)) return -1;
     if (c->scratch("sd_fused", sizeof(int32_t) * (size_t)ns, (void**)&A.fused)) return -1;
     A.km_base = d_kmb;
@@ -1921,8 +2105,18 @@ static int seed_batch(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref
     HIPCHK(hipMemsetAsync(A.fused, 0, sizeof(int32_t) * (size_t)ns, c->stream));
     // a diagonal grid cell (the query volume IS the reference volume): buckets cut behind each read's own copy
     const uint4* recs = (ref == reads && cuts_enabled(P)) ? index_ensure_cuts(c, idx) : nullptr;
-    LAUNCH(c, "seed_probe", seed_probe, ns, SEED_BLOCK, 0, (const uint32_t*)reads->d_pac, (const mhip_offset_t*)reads->d_offs, sel, ib,
-           (const uint32_t*)idx->d_starts, A, (unsigned long long*)c->d_counters, recs, recs ? idx->cut_step : 1);
+    // The bucket headers of every query k-mer (km_bstart, km_cnt: 8 bytes per lookup).  seed_strand fetches the headers of its strands
+    // itself and does not need them; the kernel chain does.  So with the strand pipeline on, seed_probe runs only when a strand has
+    // been left to the chain, then for the whole batch and without tallying the lookups a second time.
+    auto run_probe = [&](int tally) -> int {
+        if (c->scratch("sd_kmbstart", sizeof(uint32_t) * (size_t)(sumK + 1), (void**)&A.km_bstart)) return -1;
+        if (c->scratch("sd_kmcnt", sizeof(uint32_t) * (size_t)(sumK + 1), (void**)&A.km_cnt)) return -1;
+        LAUNCH(c, "seed_probe", seed_probe, ns, SEED_BLOCK, 0, (const uint32_t*)reads->d_pac, (const mhip_offset_t*)reads->d_offs, sel, ib,
+               (const uint32_t*)idx->d_starts, A, (unsigned long long*)c->d_counters, recs, recs ? idx->cut_step : 1, tally);
+        return 0;
+    };
+    const bool probe_first = !fused_enabled(P) || !fused_probe_enabled();
+    if (probe_first && run_probe(1)) return -1;
     const int gate = 2 * P->min_kmer_match;
     const int nbits = bits_for((uint32_t)(ref->num_bases / ZV));
     // (no subject can have a higher id than a query when the reference volume lies entirely before the query volume: nothing to drop)
@@ -1956,8 +2150,10 @@ static int seed_batch(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref
         if (c->scratch("sf_segscore", sizeof(int32_t) * capF, (void**)&F.seg_score)) return -1;
         if (c->scratch("sf_gated", sizeof(uint32_t) * capF, (void**)&F.gated)) return -1;
         HIPCHK(hipMemsetAsync(d_ctl, 0, sizeof(FusedCtl), c->stream));
-        LAUNCH(c, "seed_strand", seed_strand, ns, FS_THREADS, 0, (const mhip_offset_t*)reads->d_offs, sel, ib, (const uint16_t*)idx->d_slots,
-               (const int32_t*)idx->d_offsets, F, gate, std::max(0, nbits - FLT_BITS), (int)P->min_kmer_match, P->ddfs_cutoff,
+        // one workgroup per CU (its LDS holds one strand); the workgroups take the strands from a cursor in *d_ctl
+        LAUNCH(c, "seed_strand", seed_strand, std::min(ns, std::max(1, c->num_cus)), FS_THREADS, 0, (const uint32_t*)reads->d_pac,
+               (const mhip_offset_t*)reads->d_offs, sel, ib, ns, (const uint32_t*)idx->d_starts, recs, recs ? idx->cut_step : 1,
+               (const uint16_t*)idx->d_slots, (const int32_t*)idx->d_offsets, F, gate, std::max(0, nbits - FLT_BITS), (int)P->min_kmer_match, P->ddfs_cutoff,
                (unsigned long long)capF, d_ctl, (unsigned long long*)c->d_counters, RR);
         FusedCtl ctl;
         HIPCHK(hipMemcpyAsync(&ctl, d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, c->stream));
@@ -1978,6 +2174,11 @@ static int seed_batch(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref
         return 0;
     };
     if (fused_enabled(P) && run_strand_pipeline()) return -1;
+    if (nfallback > 0 && !probe_first) {
+        if (run_probe(0)) return -1;
+        B.km_bstart = A.km_bstart;
+        B.km_cnt = A.km_cnt;
+    }
 
     // ---- the kernel chain for every other strand (with the low gates of nanopore mode its own filter comes first)
     if (nfallback > 0) {
@@ -2071,6 +2272,11 @@ static bool wide_filter_enabled(const mhip_params* P) {
     const char* fe = getenv("MECAT_SEED_FILTER");      // the same knob: 0 disables every relevance filter
     const int gate = 2 * P->min_kmer_match;
     return gate >= 4 && gate < 6 && !(fe && atoi(fe) == 0);
+}
+
+static bool fused_probe_enabled() {
+    const char* e = getenv("MECAT_SEED_FUSED_PROBE");  // debug knob: 0 runs seed_probe up front and seed_strand copies its headers from the km_* arrays
+    return !(e && atoi(e) == 0);
 }
 
 static bool fused_enabled(const mhip_params* P) {
