@@ -1,5 +1,6 @@
 # Top-level build.  `make all` = everything that can be built on this machine.
 #   hip     mecat_amd/lib/libmecat_hip.so   HIP kernels + C-ABI (gfx950)
+#           mecat_amd/lib/libcns_poa_host.so   the POA window routine (csrc/cns_poa.h) compiled for the host, no HIP: the tests' expected values
 #   host    mecat_amd/bin/mecat2pw          C++ host driver (drop-in CLI) on top of the C-ABI
 #   synth   mecat_amd/lib/libsynth.so + mecat_amd/bin/synth_reads   synthetic read generator
 #   oracle  oracle/liboracle.so             CPU restatement (test infrastructure)
@@ -21,7 +22,10 @@ HOST_SRCS := $(wildcard mecat_amd/host/*.cpp)
 all: synth oracle hip host
 	@if [ -d /root/reference/src ]; then $(MAKE) ref; fi
 
-hip: $(LIBDIR)/libmecat_hip.so
+hip: $(LIBDIR)/libmecat_hip.so $(LIBDIR)/libcns_poa_host.so
+$(LIBDIR)/libcns_poa_host.so: $(CSRC)/cns_poa_host.cpp $(CSRC)/cns_poa.h
+	@mkdir -p $(LIBDIR)
+	$(CXX) -O2 -std=c++17 -fPIC -shared -Wall -I$(CSRC) $< -o $@
 build/%.o: $(CSRC)/%.hip $(HIP_HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@

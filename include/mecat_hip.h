@@ -452,8 +452,8 @@ int  mhip_debug_cns_plan(mhip_ctx* ctx, const mhip_cns_table_item* table, const 
  * out_piece_begin has *out_n_windows + 1 entries ({0} when there is no window).  MHIP_CNS_WANT_PIECES needs MHIP_CNS_WANT_PLAN (refused
  * without it); PLAN | PIECES alone copies neither strings nor tables to the host.  Without the PIECES bit the call is
  * mhip_cns_accept_templates_plan (the two outputs come back NULL, their pointers may be NULL).  mhip_cns_accept_templates_plan and _ex
- * keep refusing the bit.  The output is the same bytes on every run; release with mhip_cns_free.  The POA itself (AlnGraphBoost) and
- * the output of the corrected reads stay with the caller. */
+ * keep refusing the bit.  The output is the same bytes on every run; release with mhip_cns_free.  The POA itself (AlnGraphBoost):
+ * mhip_cns_accept_templates_poa below. */
 typedef struct { int32_t aln, col, ncols, sb_out; } mhip_cns_piece;   /* aln: index into out_accepted */
 #define MHIP_CNS_WANT_PIECES 8
 int  mhip_cns_accept_templates_pieces(mhip_ctx* ctx, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin,
@@ -474,6 +474,43 @@ int  mhip_cns_accept_templates_pieces(mhip_ctx* ctx, const mhip_volume* vol, mhi
 int  mhip_debug_cns_pieces(mhip_ctx* ctx, const char* buf, int64_t bytes, const int64_t* off, const int32_t* len, const int32_t* soff,
                            const int32_t* send, int n_pairs, const int32_t* windows, int n_windows, mhip_cns_piece** out_pieces,
                            int64_t** out_piece_begin);
+/* ---- the POA consensus of the listed windows (cns_poa.hip).  What the reference does with a listed window (sb, se, cov) is
+ * meap_cns_one_indel (mecat_correction.cpp:62-78): an AlnGraphBoost over se - sb + 1 backbone positions (MECAT_AlnGraphBoost.C:76-97), one
+ * addAln per piece with start = sb_out - sb + 1 (:99-152), mergeNodes (:219-357) and consensus((int)(cov * 0.4), cns) over bestPath
+ * (:417-458, :508-592); meap_consensus_one_segment then appends cns without its first and last letter when it has more than two
+ * (mecat_correction.cpp:104).  The device runs the same graph routine (csrc/cns_poa.h, pinned to the compiled reference by
+ * tests/test_cns_poa_ref_cpu.py through its host build libcns_poa_host.so), one window per lane: windows whose workspace fits a slot of
+ * mhip_cns_poa_small_words() 32-bit words in cns_poa_small, the others in cns_poa_large with workspaces of their own size, taken in
+ * chunks of MECAT_CNS_POA_CHUNK_BYTES (default 1 GiB).  Every window is answered on the device.
+ * mhip_cns_accept_templates_poa is mhip_cns_accept_templates_pieces with MHIP_CNS_WANT_POA allowed in `want`.  Window w of out_windows
+ * owns the bytes out_cns[out_cns_begin[w] .. out_cns_begin[w + 1]) — `cns` as meap_cns_one_indel returns it, both end letters included,
+ * no terminator; out_cns_begin has *out_n_windows + 1 entries ({0} when there is no window).  MHIP_CNS_WANT_POA needs
+ * MHIP_CNS_WANT_PLAN (refused without it).  The pieces are computed on the device whenever the bit is set and copied to the host only
+ * with MHIP_CNS_WANT_PIECES: PLAN | POA alone moves no strings, tables or pieces over the PCIe link.  Without the bit the call is
+ * mhip_cns_accept_templates_pieces (the two outputs come back NULL, their pointers may be NULL).  _pieces, _plan and _ex keep refusing
+ * the bit.  The output is the same bytes on every run; release with mhip_cns_free.  Putting the segments together from the windows'
+ * strings (meap_consensus_one_segment's target) and the output of the corrected reads stay with the caller. */
+#define MHIP_CNS_WANT_POA 16
+int  mhip_cns_accept_templates_poa(mhip_ctx* ctx, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin,
+                                   int num_templates, int tech, int min_align_size, double min_mapping_ratio, int num_threads, int want,
+                                   int min_cov, int min_size, mhip_cns_accepted** out_accepted, int64_t* out_count, char** out_strings,
+                                   int64_t* out_strings_bytes, int64_t* out_jobs, mhip_cns_table_item** out_table, uint8_t** out_ident,
+                                   int64_t** out_table_begin /* [num_templates + 1] */, mhip_cns_segment** out_segments,
+                                   int64_t** out_seg_begin /* [num_templates + 1] */, mhip_cns_window** out_windows, int64_t* out_n_windows,
+                                   int32_t** out_eranges, int64_t** out_erange_begin /* [num_templates + 1] */,
+                                   mhip_cns_piece** out_pieces, int64_t** out_piece_begin /* [*out_n_windows + 1] */,
+                                   char** out_cns, int64_t** out_cns_begin /* [*out_n_windows + 1] */);
+/* the slot of cns_poa_small in 32-bit words: a window goes there when 17 * nodes + 8 * edges <= this, with nodes = se - sb + 3 + the
+ * insertion columns of its pieces (query letter over a template gap) and edges = se - sb + 2 + their match columns + their insertion
+ * columns + the number of pieces */
+int64_t mhip_cns_poa_small_words(void);
+/* test hook: the piece kernels and then the POA kernels on ONE template: mhip_debug_cns_pieces' arguments, the windows as triples
+ * windows[3 w] = sb, windows[3 w + 1] = se, windows[3 w + 2] = cov.  Refused before anything is launched: what mhip_debug_cns_pieces
+ * refuses, and cov < 0.  -> *out_cns, *out_cns_begin [n_windows + 1] (malloc'ed, release with mhip_cns_free) */
+int  mhip_debug_cns_poa(mhip_ctx* ctx, const char* buf, int64_t bytes, const int64_t* off, const int32_t* len, const int32_t* soff,
+                        const int32_t* send, int n_pairs, const int32_t* windows, int n_windows, char** out_cns, int64_t** out_cns_begin);
+/* test hook: the last POA launch of the process: out[0] = windows that went to cns_poa_large, out[1] = launches of it (chunks) */
+void mhip_debug_cns_poa_last(int64_t* out /* [2] */);
 /* mhip_cns_free does not return a string buffer to the system at once: the library keeps the LARGEST released one (gigabytes — about
  * 14 GB for a config-2-sized batch) and hands it out again to the next batch that fits, because first-touching fresh pages costs
  * more than the batch's GPU time.  The parked buffer belongs to the process, not to a context (mhip_ctx_destroy leaves it).  This call

@@ -41,6 +41,7 @@
 #include "common.h"
 #include "cns_strings.h"
 #include "cns_pieces.h"
+#include "cns_poa_dev.h"
 #include "cns_plan.h"
 #include "cns_ranges.h"
 #include "cns_table.h"
@@ -173,6 +174,8 @@ struct PlanArgs {
     int32_t** er = nullptr; int64_t** er_begin = nullptr;
     bool want_pieces = false;      // mhip_cns_accept_templates_pieces: the windows' pieces as well
     mhip_cns_piece** pc = nullptr; int64_t** pc_begin = nullptr;
+    bool want_poa = false;         // mhip_cns_accept_templates_poa: the windows' consensus strings as well
+    char** cns = nullptr; int64_t** cns_begin = nullptr;
 };
 
 // the body of the entry points; want_tab: the outputs behind out_jobs are filled as well; plan.want: the outputs of `plan` too
@@ -181,7 +184,7 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
                            mhip_cns_accepted** out_accepted, int64_t* out_count, char** out_strings, int64_t* out_strings_bytes,
                            int64_t* out_jobs, mhip_cns_table_item** out_table, uint8_t** out_ident, int64_t** out_table_begin, const PlanArgs& plan) {
     HIPCHK(hipSetDevice(c->device));
-    const bool want_plan = plan.want, want_pieces = plan.want && plan.want_pieces, build_tab = want_tab || want_plan;      // the plan reads the table: built on the device either way, copied only when asked for
+    const bool want_plan = plan.want, want_pieces = plan.want && plan.want_pieces, want_poa = plan.want && plan.want_poa, build_tab = want_tab || want_plan;      // the plan reads the table: built on the device either way, copied only when asked for
     const int min_run = want_plan ? cns_plan_min_run(plan.min_size) : 0;
     *out_accepted = nullptr; *out_count = 0; *out_strings = nullptr; *out_strings_bytes = 0;
     if (out_jobs) *out_jobs = 0;
@@ -254,16 +257,19 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
         void* seg = nullptr; void* win = nullptr; int64_t nseg = 0, nwin = 0; long long bad = 0;
         // the slice's pieces (cns_pieces.hip): pc_cap slots of which the first pb[nwin] are records, pb[nwin + 1] counted from the slice's first
         void* pc = nullptr; int64_t* pb = nullptr; int64_t pc_cap = 0; long long pc_bad = 0;
+        // the slice's consensus strings (cns_poa.hip): cn_cap bytes of which the first cb[nwin] are strings, cb[nwin + 1] counted from the slice's first
+        void* cn = nullptr; int64_t* cb = nullptr; int64_t cn_cap = 0; long long cn_bad = 0;
     };
     // (bad: CnsPlanDev::d_bad, copied with the windows and looked at in hand_over_plan only, after every slice has run: the plan is refused
     // there; an overflow of the segment slots is refused by cns_plan_launch at once)
     struct PlanOut {
         std::vector<PlanPiece> pieces;
-        ~PlanOut() { for (PlanPiece& p : pieces) { mhip_cns_free(p.seg); mhip_cns_free(p.win); mhip_cns_free(p.pc); mhip_cns_free(p.pb); } }
+        ~PlanOut() { for (PlanPiece& p : pieces) { mhip_cns_free(p.seg); mhip_cns_free(p.win); mhip_cns_free(p.pc); mhip_cns_free(p.pb); mhip_cns_free(p.cn); mhip_cns_free(p.cb); } }
     } plan_out;
     std::vector<int64_t> SB, ERB;                 // per template: first segment; effective ranges (counts until the hand-over)
     std::vector<int32_t> ER;
     int64_t seg_total = 0, win_total = 0;
+    long long poa_large = 0, poa_chunks = 0;      // windows that went to cns_poa_large, and its launches
     if (want_plan) { SB.assign((size_t)num_templates + 1, 0); ERB.assign((size_t)num_templates + 1, 0); }
     // the windows' pieces: every slice's records behind one another, piece_begin moved from slice-local to batch-wide numbers
     auto hand_over_pieces = [&](void** out_pc, int64_t** out_pb) -> int {
@@ -302,6 +308,36 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
         *out_pc = pc; *out_pb = pb;
         return 0;
     };
+    // the windows' consensus strings: every slice's bytes behind one another, cns_begin moved from slice-local to batch-wide offsets
+    auto hand_over_poa = [&](char** out_cn, int64_t** out_cb) -> int {
+        int64_t total = 0;
+        for (const PlanPiece& p : plan_out.pieces) {
+            if (p.pc_bad) { mhip_set_error("cns pieces: an index left its array, or the pieces written are not the pieces counted"); return -1; }
+            if (p.cn_bad) { mhip_set_error("cns poa: a window's graph left its workspace bound, or a piece leaves its backbone"); return -1; }
+            if (!p.cb) continue;
+            const int64_t n = p.cb[p.nwin];
+            if (p.cb[0] != 0 || n < 0 || n > p.cn_cap) { mhip_set_error("cns poa: inconsistent counts (%lld bytes in %lld)", (long long)n, (long long)p.cn_cap); return -1; }
+            total += n;
+        }
+        int64_t* cb = (int64_t*)malloc(sizeof(int64_t) * ((size_t)win_total + 1));
+        char* cn = (char*)result_alloc((size_t)total, num_threads);
+        if (!cb || !cn) { free(cb); mhip_cns_free(cn); mhip_set_error("out of memory (%lld bytes of consensus)", (long long)total); return -1; }
+        int64_t wo = 0, base = 0;
+        for (const PlanPiece& p : plan_out.pieces) {
+            for (int64_t i = 0; i < p.nwin; ++i) cb[wo + i] = base + (p.cb ? p.cb[i] : 0);
+            wo += p.nwin;
+            if (!p.cb) continue;
+            const size_t bytes = (size_t)p.cb[p.nwin], part = (size_t)64 << 20;
+            parallel_for((int64_t)((bytes + part - 1) / part), num_threads, [&](int64_t k) {
+                const size_t o = (size_t)k * part;
+                memcpy(cn + base + o, (const char*)p.cn + o, std::min(part, bytes - o));
+            });
+            base += p.cb[p.nwin];
+        }
+        cb[wo] = base;                          // (wo == win_total)
+        *out_cn = cn; *out_cb = cb;
+        return 0;
+    };
     auto hand_over_plan = [&]() -> int {          // (after the last copy has landed)
         const size_t n1 = (size_t)num_templates + 1;
         for (const PlanPiece& p : plan_out.pieces)
@@ -309,6 +345,9 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
         void* pcs = nullptr;
         int64_t* pcb = nullptr;
         if (want_pieces && hand_over_pieces(&pcs, &pcb)) return -1;
+        char* cns = nullptr;
+        int64_t* cnb = nullptr;
+        if (want_poa && hand_over_poa(&cns, &cnb)) { mhip_cns_free(pcs); free(pcb); return -1; }
         int64_t* sb = (int64_t*)malloc(sizeof(int64_t) * n1);
         int64_t* eb = (int64_t*)malloc(sizeof(int64_t) * n1);
         int32_t* er = (int32_t*)malloc(std::max<size_t>(sizeof(int32_t) * ER.size(), 1));
@@ -316,12 +355,13 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
         if (plan_out.pieces.size() == 1) {
             seg = plan_out.pieces[0].seg; win = plan_out.pieces[0].win;
             mhip_cns_free(plan_out.pieces[0].pc); mhip_cns_free(plan_out.pieces[0].pb);      // (pc: NULL when it became the result)
+            mhip_cns_free(plan_out.pieces[0].cn); mhip_cns_free(plan_out.pieces[0].cb);
             plan_out.pieces.clear();
         } else {
             seg = result_alloc(sizeof(mhip_cns_segment) * (size_t)seg_total, num_threads);
             win = result_alloc(sizeof(mhip_cns_window) * (size_t)win_total, num_threads);
         }
-        if (!sb || !eb || !er || !seg || !win) { free(sb); free(eb); free(er); mhip_cns_free(seg); mhip_cns_free(win); mhip_cns_free(pcs); free(pcb); mhip_set_error("out of memory"); return -1; }
+        if (!sb || !eb || !er || !seg || !win) { free(sb); free(eb); free(er); mhip_cns_free(seg); mhip_cns_free(win); mhip_cns_free(pcs); free(pcb); mhip_cns_free(cns); free(cnb); mhip_set_error("out of memory"); return -1; }
         size_t so = 0, wo = 0;
         for (PlanPiece& p : plan_out.pieces) {
             const size_t sbytes = sizeof(mhip_cns_segment) * (size_t)p.nseg, wbytes = sizeof(mhip_cns_window) * (size_t)p.nwin, piece = (size_t)64 << 20;
@@ -338,6 +378,7 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
         if (!ER.empty()) memcpy(er, ER.data(), sizeof(int32_t) * ER.size());
         *plan.seg = (mhip_cns_segment*)seg; *plan.seg_begin = sb; *plan.win = (mhip_cns_window*)win; *plan.n_win = win_total; *plan.er = er; *plan.er_begin = eb;
         if (want_pieces) { *plan.pc = (mhip_cns_piece*)pcs; *plan.pc_begin = pcb; }
+        if (want_poa) { *plan.cns = cns; *plan.cns_begin = cnb; }
         return 0;
     };
     auto hand_over = [&]() -> int {
@@ -610,6 +651,7 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
         // the slice's plan, behind cns_table_finish on the same stream and in front of the copies
         CnsPlanDev pd;
         CnsPiecesDev qd;
+        CnsPoaDev od;
         PlanPiece piece;
         if (want_plan && tw) {
             const int nt = sl.t1 - sl.t0;
@@ -630,7 +672,7 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
             plan_out.pieces.push_back(piece);
             if (!piece.seg || !piece.win) { mhip_set_error("out of memory (%lld windows)", (long long)pd.nwin); return -1; }
             // the windows' pieces, behind cns_plan_emit on the same stream and in front of the copies: the slice's strings and plan are in place
-            if (want_pieces && pd.nwin > 0 && na > 0) {
+            if ((want_pieces || want_poa) && pd.nwin > 0 && na > 0) {
                 std::vector<CnsPieceItem> pitems((size_t)na);
                 std::vector<long long> afl((size_t)nt + 1);
                 for (int tl = 0; tl <= nt; ++tl) afl[(size_t)tl] = (long long)sl.afirst[(size_t)tl];
@@ -645,10 +687,22 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
                                       pd.nwin, &qd)) return -1;
                 tk[6] += qd.wait_s;
                 PlanPiece& pp = plan_out.pieces.back();
-                pp.pc_cap = qd.cap;
-                pp.pc = result_alloc(sizeof(mhip_cns_piece) * (size_t)qd.cap, num_threads);
-                pp.pb = (int64_t*)result_alloc(sizeof(int64_t) * ((size_t)pd.nwin + 1), num_threads);
-                if (!pp.pc || !pp.pb) { mhip_set_error("out of memory (%lld pieces)", (long long)qd.cap); return -1; }
+                if (want_pieces) {
+                    pp.pc_cap = qd.cap;
+                    pp.pc = result_alloc(sizeof(mhip_cns_piece) * (size_t)qd.cap, num_threads);
+                    pp.pb = (int64_t*)result_alloc(sizeof(int64_t) * ((size_t)pd.nwin + 1), num_threads);
+                    if (!pp.pc || !pp.pb) { mhip_set_error("out of memory (%lld pieces)", (long long)qd.cap); return -1; }
+                }
+                // the windows' consensus, behind cns_pieces_emit on the same stream: the pieces stay where they are
+                if (want_poa) {
+                    if (cns_poa_launch(c, b, d_str, qd, na, (long long)a0, pd.d_win, pd.nwin, &od)) return -1;
+                    tk[6] += od.wait_s;
+                    poa_large += od.nlarge; poa_chunks += od.nchunks;
+                    pp.cn_cap = od.cap;
+                    pp.cn = result_alloc((size_t)od.cap, num_threads);
+                    pp.cb = (int64_t*)result_alloc(sizeof(int64_t) * ((size_t)pd.nwin + 1), num_threads);
+                    if (!pp.cn || !pp.cb) { mhip_set_error("out of memory (%lld bytes of consensus)", (long long)od.cap); return -1; }
+                }
             }
             seg_total += pd.nseg; win_total += pd.nwin;
         }
@@ -663,9 +717,17 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
         if (pd.d_bad) HIPCHK(hipMemcpyAsync(&plan_out.pieces.back().bad, pd.d_bad, sizeof(long long), hipMemcpyDeviceToHost, copy_stream));      // (pieces: reserved, nothing moves)
         if (qd.d_pb) {                          // (the slots the bound allows; how many hold records is pb[nwin], read at the hand-over)
             PlanPiece& pp = plan_out.pieces.back();
-            if (qd.cap) HIPCHK(hipMemcpyAsync(pp.pc, qd.d_pieces, sizeof(mhip_cns_piece) * (size_t)qd.cap, hipMemcpyDeviceToHost, copy_stream));
-            HIPCHK(hipMemcpyAsync(pp.pb, qd.d_pb, sizeof(int64_t) * ((size_t)pd.nwin + 1), hipMemcpyDeviceToHost, copy_stream));
+            if (want_pieces) {
+                if (qd.cap) HIPCHK(hipMemcpyAsync(pp.pc, qd.d_pieces, sizeof(mhip_cns_piece) * (size_t)qd.cap, hipMemcpyDeviceToHost, copy_stream));
+                HIPCHK(hipMemcpyAsync(pp.pb, qd.d_pb, sizeof(int64_t) * ((size_t)pd.nwin + 1), hipMemcpyDeviceToHost, copy_stream));
+            }
             HIPCHK(hipMemcpyAsync(&pp.pc_bad, qd.d_bad, sizeof(long long), hipMemcpyDeviceToHost, copy_stream));
+        }
+        if (od.d_cb) {                          // (the bytes the bound allows; how many hold strings is cb[nwin], read at the hand-over)
+            PlanPiece& pp = plan_out.pieces.back();
+            if (od.cap) HIPCHK(hipMemcpyAsync(pp.cn, od.d_cns, (size_t)od.cap, hipMemcpyDeviceToHost, copy_stream));
+            HIPCHK(hipMemcpyAsync(pp.cb, od.d_cb, sizeof(int64_t) * ((size_t)pd.nwin + 1), hipMemcpyDeviceToHost, copy_stream));
+            HIPCHK(hipMemcpyAsync(&pp.cn_bad, od.d_bad, sizeof(long long), hipMemcpyDeviceToHost, copy_stream));
         }
         if (tw && want_tab) {
             HIPCHK(hipMemcpyAsync(tab_out.tab + tw0, d_tab, sizeof(uint32_t) * (size_t)tw, hipMemcpyDeviceToHost, copy_stream));
@@ -714,6 +776,9 @@ static int cns_accept_body(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candida
                 (double)sbytes / 1e9, tk[0], tk[1], tk[2], tk[3], tk[4], tk[5]);
     if (times && want_pieces)
         fprintf(stderr, "[cns_accept] pieces: %lld pieces (the waits for their bound are counted with the plan's)\n", (long long)(*plan.pc_begin)[win_total]);
+    if (times && want_poa)
+        fprintf(stderr, "[cns_accept] poa: %lld bytes of consensus, %lld windows in cns_poa_large (%lld launches); the waits for the bounds are counted with the plan's\n",
+                (long long)(*plan.cns_begin)[win_total], poa_large, poa_chunks);
     if (times && want_plan)
         fprintf(stderr, "[cns_accept] plan: %lld segments, %lld windows: waited for the counts %.3f s (within strings launched), slices' pieces put together %.3f (within last copies)\n",
                 (long long)seg_total, (long long)win_total, tk[6], tk[7]);
@@ -746,22 +811,25 @@ int mhip_cns_accept_templates_ex(mhip_ctx* c, const mhip_volume* vol, mhip_ext_c
                            out_accepted, out_count, out_strings, out_strings_bytes, out_jobs, out_table, out_ident, out_table_begin, PlanArgs());
 }
 
-// the body of mhip_cns_accept_templates_plan and mhip_cns_accept_templates_pieces; `allowed`: the bits of `want` the entry point takes
+// the body of mhip_cns_accept_templates_plan, _pieces and _poa; `allowed`: the bits of `want` the entry point takes
 static int cns_accept_plan_entry(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin, int num_templates, int tech,
                                  int min_align_size, double min_mapping_ratio, int num_threads, int want, int allowed, int min_cov, int min_size,
                                  mhip_cns_accepted** out_accepted, int64_t* out_count, char** out_strings, int64_t* out_strings_bytes, int64_t* out_jobs,
                                  mhip_cns_table_item** out_table, uint8_t** out_ident, int64_t** out_table_begin, mhip_cns_segment** out_segments,
                                  int64_t** out_seg_begin, mhip_cns_window** out_windows, int64_t* out_n_windows, int32_t** out_eranges, int64_t** out_erange_begin,
-                                 mhip_cns_piece** out_pieces, int64_t** out_piece_begin) {
+                                 mhip_cns_piece** out_pieces, int64_t** out_piece_begin, char** out_cns, int64_t** out_cns_begin) {
     const bool want_tab = (want & MHIP_CNS_WANT_TABLE) != 0;
     PlanArgs plan;
     plan.want = (want & MHIP_CNS_WANT_PLAN) != 0;
     plan.want_pieces = (want & MHIP_CNS_WANT_PIECES) != 0;
+    plan.want_poa = (want & MHIP_CNS_WANT_POA) != 0;
     if (want == 0 || (want & ~allowed)) {
-        mhip_set_error("cns accept: want = %d (MHIP_CNS_WANT_STRINGS | MHIP_CNS_WANT_TABLE | MHIP_CNS_WANT_PLAN%s)", want, (allowed & MHIP_CNS_WANT_PIECES) ? " | MHIP_CNS_WANT_PIECES" : "");
+        mhip_set_error("cns accept: want = %d (MHIP_CNS_WANT_STRINGS | MHIP_CNS_WANT_TABLE | MHIP_CNS_WANT_PLAN%s)", want, (allowed & MHIP_CNS_WANT_POA) ? " | MHIP_CNS_WANT_PIECES | MHIP_CNS_WANT_POA" : (allowed & MHIP_CNS_WANT_PIECES) ? " | MHIP_CNS_WANT_PIECES" : "");
         return -1;
     }
     if (plan.want_pieces && !plan.want) { mhip_set_error("cns accept: want = %d: MHIP_CNS_WANT_PIECES needs MHIP_CNS_WANT_PLAN (pieces belong to the plan's windows)", want); return -1; }
+    if (plan.want_poa && !plan.want) { mhip_set_error("cns accept: want = %d: MHIP_CNS_WANT_POA needs MHIP_CNS_WANT_PLAN (the consensus belongs to the plan's windows)", want); return -1; }
+    if (plan.want_poa && (!out_cns || !out_cns_begin)) { mhip_set_error("cns accept: the consensus was asked for without a place to put it"); return -1; }
     if (plan.want_pieces && (!out_pieces || !out_piece_begin)) { mhip_set_error("cns accept: the pieces were asked for without a place to put them"); return -1; }
     if (want_tab && (!out_table || !out_ident || !out_table_begin)) { mhip_set_error("cns accept: the table was asked for without a place to put it"); return -1; }
     if (plan.want && (!out_segments || !out_seg_begin || !out_windows || !out_n_windows || !out_eranges || !out_erange_begin)) {
@@ -780,7 +848,10 @@ static int cns_accept_plan_entry(mhip_ctx* c, const mhip_volume* vol, mhip_ext_c
     if (out_erange_begin) *out_erange_begin = nullptr;
     if (out_pieces) *out_pieces = nullptr;
     if (out_piece_begin) *out_piece_begin = nullptr;
+    if (out_cns) *out_cns = nullptr;
+    if (out_cns_begin) *out_cns_begin = nullptr;
     plan.pc = out_pieces; plan.pc_begin = out_piece_begin;
+    plan.cns = out_cns; plan.cns_begin = out_cns_begin;
     plan.min_cov = min_cov; plan.min_size = min_size;
     plan.seg = out_segments; plan.seg_begin = out_seg_begin; plan.win = out_windows; plan.n_win = out_n_windows; plan.er = out_eranges; plan.er_begin = out_erange_begin;
     return cns_accept_body(c, vol, cands, tmpl_begin, num_templates, tech, min_align_size, min_mapping_ratio, num_threads, (want & MHIP_CNS_WANT_STRINGS) != 0, want_tab,
@@ -795,7 +866,7 @@ int mhip_cns_accept_templates_plan(mhip_ctx* c, const mhip_volume* vol, mhip_ext
     return cns_accept_plan_entry(c, vol, cands, tmpl_begin, num_templates, tech, min_align_size, min_mapping_ratio, num_threads, want,
                                  MHIP_CNS_WANT_STRINGS | MHIP_CNS_WANT_TABLE | MHIP_CNS_WANT_PLAN, min_cov, min_size, out_accepted, out_count, out_strings, out_strings_bytes,
                                  out_jobs, out_table, out_ident, out_table_begin, out_segments, out_seg_begin, out_windows, out_n_windows, out_eranges, out_erange_begin,
-                                 nullptr, nullptr);
+                                 nullptr, nullptr, nullptr, nullptr);
 }
 
 int mhip_cns_accept_templates_pieces(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin, int num_templates, int tech,
@@ -807,7 +878,19 @@ int mhip_cns_accept_templates_pieces(mhip_ctx* c, const mhip_volume* vol, mhip_e
     return cns_accept_plan_entry(c, vol, cands, tmpl_begin, num_templates, tech, min_align_size, min_mapping_ratio, num_threads, want,
                                  MHIP_CNS_WANT_STRINGS | MHIP_CNS_WANT_TABLE | MHIP_CNS_WANT_PLAN | MHIP_CNS_WANT_PIECES, min_cov, min_size, out_accepted, out_count, out_strings,
                                  out_strings_bytes, out_jobs, out_table, out_ident, out_table_begin, out_segments, out_seg_begin, out_windows, out_n_windows, out_eranges,
-                                 out_erange_begin, out_pieces, out_piece_begin);
+                                 out_erange_begin, out_pieces, out_piece_begin, nullptr, nullptr);
+}
+
+int mhip_cns_accept_templates_poa(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin, int num_templates, int tech,
+                                  int min_align_size, double min_mapping_ratio, int num_threads, int want, int min_cov, int min_size,
+                                  mhip_cns_accepted** out_accepted, int64_t* out_count, char** out_strings, int64_t* out_strings_bytes, int64_t* out_jobs,
+                                  mhip_cns_table_item** out_table, uint8_t** out_ident, int64_t** out_table_begin, mhip_cns_segment** out_segments,
+                                  int64_t** out_seg_begin, mhip_cns_window** out_windows, int64_t* out_n_windows, int32_t** out_eranges, int64_t** out_erange_begin,
+                                  mhip_cns_piece** out_pieces, int64_t** out_piece_begin, char** out_cns, int64_t** out_cns_begin) {
+    return cns_accept_plan_entry(c, vol, cands, tmpl_begin, num_templates, tech, min_align_size, min_mapping_ratio, num_threads, want,
+                                 MHIP_CNS_WANT_STRINGS | MHIP_CNS_WANT_TABLE | MHIP_CNS_WANT_PLAN | MHIP_CNS_WANT_PIECES | MHIP_CNS_WANT_POA, min_cov, min_size, out_accepted,
+                                 out_count, out_strings, out_strings_bytes, out_jobs, out_table, out_ident, out_table_begin, out_segments, out_seg_begin, out_windows,
+                                 out_n_windows, out_eranges, out_erange_begin, out_pieces, out_piece_begin, out_cns, out_cns_begin);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@ struct CnsPieceItem {
 struct CnsPiecesDev {
     const mhip_cns_piece* d_pieces = nullptr;     // [cap] slots; the first d_pb[nwin] hold the records, final (global `aln`)
     const long long* d_pb = nullptr;              // [nwin + 1] first piece of every window, counted from the launch's first piece
+    const CnsPieceItem* d_items = nullptr;        // [na] the launch's items[] on the device (what cns_poa.hip finds a piece's strings with)
     const long long* d_bad = nullptr;             // nonzero once the kernels have run: an index derived from the data left its array (NULL: nothing ran)
     long long cap = 0;                            // the bound on the pieces the buffers were sized by: sum over the alignments of the windows they overlap
     double wait_s = 0;                            // host seconds spent in the wait for that bound
@@ -28,3 +29,10 @@ struct CnsPiecesDev {
 int cns_pieces_launch(mhip_ctx* c, int set, const char* d_str, const CnsPieceItem* items, long long na, long long aln_base, int nt, int t_index0,
                       const long long* afirst, const long long* tb, const mhip_cns_segment* d_seg, long long nseg, const long long* d_segb, long long seg_base,
                       long long win_base, const mhip_cns_window* d_win, long long nwin, CnsPiecesDev* out);
+
+// The front half of the test hooks mhip_debug_cns_pieces and mhip_debug_cns_poa: ONE template's alignments as host strings (see
+// mecat_hip.h) and n_windows windows of `wstride` ints each — (sb, se) or (sb, se, cov) — checked, uploaded and run through
+// cns_pieces_launch (set 0).  n_windows == 0 launches nothing and leaves *pd empty.  *d_buf: the strings on the device, *d_win the
+// window records (cov 0 with wstride 2); both are scratch of `c`.
+int cns_pieces_debug_launch(mhip_ctx* c, const char* buf, int64_t bytes, const int64_t* off, const int32_t* len, const int32_t* soff, const int32_t* send, int n_pairs,
+                            const int32_t* windows, int wstride, int n_windows, CnsPiecesDev* pd, const char** d_buf, const mhip_cns_window** d_win);

@@ -317,18 +317,13 @@ int cns_pieces_launch(mhip_ctx* c, int set, const char* d_str, const CnsPieceIte
     LAUNCH(c, "cns_pieces_emit", cns_pieces_walk<true>, waves(nwin), 256, 0, d_win, nwin, d_wtl, nt, d_twb, d_afirst, d_items, na, aln_base, d_rng, d_abase, T, d_cols, d_cole,
            (int32_t*)nullptr, d_pb, d_pieces, d_tot + 1);
     HIPCHK(hipGetLastError());
-    out->d_pieces = d_pieces; out->d_pb = d_pb; out->d_bad = d_tot + 1; out->cap = T;
+    out->d_pieces = d_pieces; out->d_pb = d_pb; out->d_items = d_items; out->d_bad = d_tot + 1; out->cap = T;
     return 0;
 }
 
-extern "C" {
-
-// TEST HOOK (tests/test_gpu_cns_pieces.py): the kernels above on one template, host strings and a host window list; see mecat_hip.h
-int mhip_debug_cns_pieces(mhip_ctx* c, const char* buf, int64_t bytes, const int64_t* off, const int32_t* len, const int32_t* soff, const int32_t* send, int n_pairs,
-                          const int32_t* windows, int n_windows, mhip_cns_piece** out_pieces, int64_t** out_piece_begin) {
-    HIPCHK(hipSetDevice(c->device));
-    if (!out_pieces || !out_piece_begin) { mhip_set_error("cns pieces: an output pointer is NULL"); return -1; }
-    *out_pieces = nullptr; *out_piece_begin = nullptr;
+int cns_pieces_debug_launch(mhip_ctx* c, const char* buf, int64_t bytes, const int64_t* off, const int32_t* len, const int32_t* soff, const int32_t* send, int n_pairs,
+                            const int32_t* windows, int wstride, int n_windows, CnsPiecesDev* pd, const char** d_buf_out, const mhip_cns_window** d_win_out) {
+    *pd = CnsPiecesDev(); *d_buf_out = nullptr; *d_win_out = nullptr;
     if (n_pairs < 0 || n_pairs > 100) { mhip_set_error("cns pieces: %d pairs (at most 100: MAX_CNS_OVLPS)", n_pairs); return -1; }
     if (n_windows < 0) { mhip_set_error("cns pieces: %d windows", n_windows); return -1; }
     long long L = 1;
@@ -350,39 +345,55 @@ int mhip_debug_cns_pieces(mhip_ctx* c, const char* buf, int64_t bytes, const int
     }
     std::vector<mhip_cns_window> win((size_t)n_windows);
     for (int w = 0; w < n_windows; ++w) {
-        const int32_t sb = windows[2 * w], se = windows[2 * w + 1];
+        const int32_t sb = windows[(size_t)wstride * w], se = windows[(size_t)wstride * w + 1];
         if (sb < 0 || se < 0) { mhip_set_error("cns pieces: window %d has negative coordinates", w); return -1; }
         if (sb >= se) { mhip_set_error("cns pieces: window %d is not sb < se (%d, %d)", w, sb, se); return -1; }
-        if (w && windows[2 * w - 1] > sb) { mhip_set_error("cns pieces: windows %d and %d are not ascending and disjoint", w - 1, w); return -1; }
+        if (w && windows[(size_t)wstride * (w - 1) + 1] > sb) { mhip_set_error("cns pieces: windows %d and %d are not ascending and disjoint", w - 1, w); return -1; }
         if (se > 0x3fffffff) { mhip_set_error("cns pieces: window %d ends at %d", w, se); return -1; }
-        win[(size_t)w].sb = sb; win[(size_t)w].se = se; win[(size_t)w].cov = 0; win[(size_t)w].segment = 0;
+        win[(size_t)w].sb = sb; win[(size_t)w].se = se; win[(size_t)w].cov = wstride > 2 ? windows[(size_t)wstride * w + 2] : 0; win[(size_t)w].segment = 0;
         L = std::max<long long>(L, se);
     }
+    if (n_windows == 0) return 0;
+    mhip_cns_segment sg;
+    sg.template_index = 0; sg.beg = 0; sg.end = (int32_t)L; sg.n_anchors = 0; sg.win_begin = 0; sg.win_end = n_windows;
+    const long long segb[2] = {0, 1}, afirst[2] = {0, n_pairs}, tb[2] = {0, L};
+    char* d_buf;
+    mhip_cns_window* d_win;
+    mhip_cns_segment* d_seg;
+    long long* d_segb;
+    if (c->scratch("cqd_buf", (size_t)std::max<int64_t>(bytes, 1) + 128, (void**)&d_buf)) return -1;
+    if (c->scratch("cqd_win", sizeof(mhip_cns_window) * (size_t)n_windows, (void**)&d_win)) return -1;
+    if (c->scratch("cqd_seg", sizeof(mhip_cns_segment), (void**)&d_seg)) return -1;
+    if (c->scratch("cqd_segb", sizeof(segb), (void**)&d_segb)) return -1;
+    if (bytes > 0) HIPCHK(hipMemcpyAsync(d_buf, buf, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_win, win.data(), sizeof(mhip_cns_window) * (size_t)n_windows, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_seg, &sg, sizeof(sg), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_segb, segb, sizeof(segb), hipMemcpyHostToDevice, c->stream));
+    // (cns_pieces_launch waits for the stream behind these uploads: the host arrays live long enough)
+    if (cns_pieces_launch(c, 0, d_buf, items.data(), n_pairs, 0, 1, 0, afirst, tb, d_seg, 1, d_segb, 0, 0, d_win, n_windows, pd)) return -1;
+    *d_buf_out = d_buf; *d_win_out = d_win;
+    return 0;
+}
+
+extern "C" {
+
+// TEST HOOK (tests/test_gpu_cns_pieces.py): the kernels above on one template, host strings and a host window list; see mecat_hip.h
+int mhip_debug_cns_pieces(mhip_ctx* c, const char* buf, int64_t bytes, const int64_t* off, const int32_t* len, const int32_t* soff, const int32_t* send, int n_pairs,
+                          const int32_t* windows, int n_windows, mhip_cns_piece** out_pieces, int64_t** out_piece_begin) {
+    HIPCHK(hipSetDevice(c->device));
+    if (!out_pieces || !out_piece_begin) { mhip_set_error("cns pieces: an output pointer is NULL"); return -1; }
+    *out_pieces = nullptr; *out_piece_begin = nullptr;
+    CnsPiecesDev pd;
+    const char* d_buf;
+    const mhip_cns_window* d_win;
+    if (cns_pieces_debug_launch(c, buf, bytes, off, len, soff, send, n_pairs, windows, 2, n_windows, &pd, &d_buf, &d_win)) return -1;
     struct Out {
         void *pc = nullptr, *pb = nullptr;
         ~Out() { free(pc); free(pb); }
     } o;
     o.pb = calloc((size_t)n_windows + 1, sizeof(int64_t));
     if (!o.pb) { mhip_set_error("out of memory"); return -1; }
-    CnsPiecesDev pd;
     if (n_windows > 0) {
-        mhip_cns_segment sg;
-        sg.template_index = 0; sg.beg = 0; sg.end = (int32_t)L; sg.n_anchors = 0; sg.win_begin = 0; sg.win_end = n_windows;
-        const long long segb[2] = {0, 1}, afirst[2] = {0, n_pairs}, tb[2] = {0, L};
-        char* d_buf;
-        mhip_cns_window* d_win;
-        mhip_cns_segment* d_seg;
-        long long* d_segb;
-        if (c->scratch("cqd_buf", (size_t)std::max<int64_t>(bytes, 1) + 128, (void**)&d_buf)) return -1;
-        if (c->scratch("cqd_win", sizeof(mhip_cns_window) * (size_t)n_windows, (void**)&d_win)) return -1;
-        if (c->scratch("cqd_seg", sizeof(mhip_cns_segment), (void**)&d_seg)) return -1;
-        if (c->scratch("cqd_segb", sizeof(segb), (void**)&d_segb)) return -1;
-        if (bytes > 0) HIPCHK(hipMemcpyAsync(d_buf, buf, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(d_win, win.data(), sizeof(mhip_cns_window) * (size_t)n_windows, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(d_seg, &sg, sizeof(sg), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(d_segb, segb, sizeof(segb), hipMemcpyHostToDevice, c->stream));
-        // (cns_pieces_launch waits for the stream behind these uploads: the host arrays live long enough)
-        if (cns_pieces_launch(c, 0, d_buf, items.data(), n_pairs, 0, 1, 0, afirst, tb, d_seg, 1, d_segb, 0, 0, d_win, n_windows, &pd)) return -1;
         long long bad = 0;
         HIPCHK(hipMemcpyAsync(o.pb, pd.d_pb, sizeof(long long) * ((size_t)n_windows + 1), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(&bad, pd.d_bad, sizeof(long long), hipMemcpyDeviceToHost, c->stream));

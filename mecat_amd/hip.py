@@ -132,6 +132,10 @@ def lib():
                                       C.POINTER(vp)]
     L.mhip_cns_accept_templates_pieces.argtypes = L.mhip_cns_accept_templates_plan.argtypes + [C.POINTER(vp), C.POINTER(vp)]
     L.mhip_debug_cns_pieces.argtypes = [vp, vp, i64, vp, vp, vp, vp, i32, vp, i32, C.POINTER(vp), C.POINTER(vp)]
+    L.mhip_cns_accept_templates_poa.argtypes = L.mhip_cns_accept_templates_pieces.argtypes + [C.POINTER(vp), C.POINTER(vp)]
+    L.mhip_debug_cns_poa.argtypes = [vp, vp, i64, vp, vp, vp, vp, i32, vp, i32, C.POINTER(vp), C.POINTER(vp)]
+    L.mhip_cns_poa_small_words.restype = i64
+    L.mhip_cns_poa_small_words.argtypes = []
     L.mhip_cns_free.argtypes = [vp]
     L.mhip_host_alloc.argtypes = [C.c_size_t, C.POINTER(vp)]
     L.mhip_host_free.argtypes = [vp]
@@ -648,6 +652,61 @@ def debug_cns_pieces(ctx, buf, off, lens, soff, send, windows):
                                      len(win), C.byref(pc), C.byref(pcb)))
     piece_begin = _cns_take(pcb, np.int64, len(win) + 1)
     return _cns_take(pc, PIECE_DTYPE, int(piece_begin[-1])), piece_begin
+
+
+CNS_WANT_POA = 16
+
+
+def cns_poa_small_words():
+    """the slot of cns_poa_small in 32-bit words (a window goes there when 17 * nodes + 8 * edges fits; see mecat_hip.h)"""
+    return int(lib().mhip_cns_poa_small_words())
+
+
+def cns_accept_templates_poa(ctx, vol, cands, tmpl_begin, tech, min_align_size, min_mapping_ratio, want, min_cov, min_size, threads=8):
+    """cns_accept_templates_pieces with CNS_WANT_POA allowed in `want` (it needs CNS_WANT_PLAN): the POA consensus of every listed window,
+    computed on the device — meap_cns_one_indel's `cns` (AlnGraphBoost: addAln of the window's pieces, mergeNodes, consensus at
+    (int)(cov * 0.4)).  The plan dict gets two more entries: cns [uint8] and cns_begin [windows + 1]; window w owns cns[cns_begin[w]:
+    cns_begin[w + 1]], both end letters included.  Without CNS_WANT_POA the result is cns_accept_templates_pieces'.  The pieces are
+    copied from the device only with CNS_WANT_PIECES; CNS_WANT_PLAN | CNS_WANT_POA alone copies no strings, tables or pieces."""
+    cands = np.ascontiguousarray(cands)
+    tb = np.ascontiguousarray(tmpl_begin, dtype=np.int64)
+    acc, st, tab, idn, tbeg = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    seg, segb, win, er, erb, pc, pcb, cn, cnb = (C.c_void_p() for _ in range(9))
+    na, sb, nj, nwin = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    _chk(lib().mhip_cns_accept_templates_poa(ctx.h, vol.h, cands.ctypes.data, tb.ctypes.data, len(tb) - 1, tech, min_align_size, float(min_mapping_ratio), threads,
+                                             int(want), int(min_cov), int(min_size), C.byref(acc), C.byref(na), C.byref(st), C.byref(sb), C.byref(nj), C.byref(tab),
+                                             C.byref(idn), C.byref(tbeg), C.byref(seg), C.byref(segb), C.byref(win), C.byref(nwin), C.byref(er), C.byref(erb),
+                                             C.byref(pc), C.byref(pcb), C.byref(cn), C.byref(cnb)))
+    a = _cns_take(acc, ACCEPTED_DTYPE, na.value)
+    s = _cns_buffer(st, sb.value)
+    begin = _cns_take(tbeg, np.int64, len(tb))
+    nw = int(begin[-1]) if len(begin) else 0
+    plan = _cns_plan_out(seg, segb, win, nwin, er, erb, len(tb) - 1) if int(want) & CNS_WANT_PLAN else None
+    if plan is not None and int(want) & CNS_WANT_PIECES:
+        plan["piece_begin"] = _cns_take(pcb, np.int64, int(nwin.value) + 1)
+        npc = int(plan["piece_begin"][-1]) if len(plan["piece_begin"]) else 0
+        plan["pieces"] = _cns_buffer(pc, npc * PIECE_DTYPE.itemsize).view(PIECE_DTYPE)
+    if plan is not None and int(want) & CNS_WANT_POA:
+        plan["cns_begin"] = _cns_take(cnb, np.int64, int(nwin.value) + 1)
+        plan["cns"] = _cns_buffer(cn, int(plan["cns_begin"][-1]) if len(plan["cns_begin"]) else 0)
+    return a, s, nj.value, _cns_buffer(tab, 4 * nw).view(TABLE_DTYPE), _cns_buffer(idn, nw), begin, plan
+
+
+def debug_cns_poa(ctx, buf, off, lens, soff, send, windows):
+    """test hook: the piece kernels and then the POA kernels on one template.  debug_cns_pieces' arguments with windows [k, 3] int32
+    (sb, se, cov).  -> (cns [uint8], cns_begin [k + 1])"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    lens = np.ascontiguousarray(lens, dtype=np.int32)
+    soff = np.ascontiguousarray(soff, dtype=np.int32)
+    send = np.ascontiguousarray(send, dtype=np.int32)
+    win = np.ascontiguousarray(windows, dtype=np.int32).reshape(-1, 3)
+    assert len(off) == len(lens) == len(soff) == len(send)
+    cn, cnb = C.c_void_p(), C.c_void_p()
+    _chk(lib().mhip_debug_cns_poa(ctx.h, buf.ctypes.data, len(buf), off.ctypes.data, lens.ctypes.data, soff.ctypes.data, send.ctypes.data, len(off), win.ctypes.data,
+                                  len(win), C.byref(cn), C.byref(cnb)))
+    cns_begin = _cns_take(cnb, np.int64, len(win) + 1)
+    return _cns_take(cn, np.uint8, int(cns_begin[-1])), cns_begin
 
 
 COMM_ID_BYTES = 128
