@@ -261,8 +261,7 @@ int cns_pieces_launch(mhip_ctx* c, int set, const char* d_str, const CnsPieceIte
     if (nwin > 0x7fffffffLL || aln_base + na > 0x7fffffffLL) { mhip_set_error("cns pieces: too many windows or alignments in one batch"); return -1; }
     const long long W = tb[nt] - tb[0];         // template positions of the launch
     if (tb[0] != 0 || W <= 0) { mhip_set_error("cns pieces: the templates' positions must start at 0"); return -1; }
-    const std::string sfx = set ? "1" : "";
-    auto buf = [&](const char* name, size_t bytes, void** p) { return c->scratch((std::string(name) + sfx).c_str(), std::max<size_t>(bytes, 16), p); };
+    auto buf = [&](const char* name, size_t bytes, void** p) { return scratch_set(c, name, set, std::max<size_t>(bytes, 16), p); };
     std::vector<long long> head(2 * ((size_t)nt + 1));      // afirst, tb: one upload
     memcpy(head.data(), afirst, sizeof(long long) * ((size_t)nt + 1));
     memcpy(head.data() + (size_t)nt + 1, tb, sizeof(long long) * ((size_t)nt + 1));

@@ -234,8 +234,7 @@ int cns_plan_launch(mhip_ctx* c, int set, const uint32_t* d_table, const uint8_t
     if (seg_base + S > 0x7fffffffLL) { mhip_set_error("cns plan: too many segments in one batch"); return -1; }
     memcpy(head.data(), tb, sizeof(long long) * ((size_t)nt + 1));
     memcpy(head.data() + (size_t)nt + 1, rb, sizeof(long long) * ((size_t)nt + 1));
-    const std::string sfx = set ? "1" : "";
-    auto buf = [&](const char* name, size_t bytes, void** p) { return c->scratch((std::string(name) + sfx).c_str(), std::max<size_t>(bytes, 16), p); };
+    auto buf = [&](const char* name, size_t bytes, void** p) { return scratch_set(c, name, set, std::max<size_t>(bytes, 16), p); };
     long long *d_head, *d_segb, *d_wb, *d_tot;
     int32_t *d_er, *d_cnt, *d_wcnt;
     mhip_cns_segment *d_slots, *d_seg;

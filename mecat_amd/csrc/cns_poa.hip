@@ -210,8 +210,7 @@ int cns_poa_launch(mhip_ctx* c, int set, const char* d_str, const CnsPiecesDev& 
     *out = CnsPoaDev();
     if (nwin <= 0) return 0;
     if (nwin > 0x7fffffffLL) { mhip_set_error("cns poa: too many windows in one batch"); return -1; }
-    const std::string sfx = set ? "1" : "";
-    auto buf = [&](const char* name, size_t bytes, void** p) { return c->scratch((std::string(name) + sfx).c_str(), std::max<size_t>(bytes, 16), p); };
+    auto buf = [&](const char* name, size_t bytes, void** p) { return scratch_set(c, name, set, std::max<size_t>(bytes, 16), p); };
     const size_t n1 = (size_t)nwin + 1;
     int2* d_caps;
     long long *d_ob, *d_li, *d_lw, *d_tot, *d_cb;

@@ -76,6 +76,11 @@ struct mhip_ctx {
     hipEvent_t get_event();
 };
 
+// scratch() for code that works through two sets of buffers in turn: set 1's buffer is `name` + "1"
+inline int scratch_set(mhip_ctx* c, const char* name, int set, size_t bytes, void** out) {
+    return c->scratch(set ? (std::string(name) + "1").c_str() : name, bytes, out);
+}
+
 struct mhip_volume {
     int device = 0;
     int num_reads = 0;

@@ -120,19 +120,17 @@ def lib():
     L.mhip_seed_reads_sharded.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(Params), vp, vp]
     L.mhip_align_sharded.argtypes = [vp, vp, vp, i32, i32, vp, C.POINTER(i64)]
     L.mhip_sharded_tables.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
-    L.mhip_cns_accept_templates.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, C.c_double, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp),
-                                            C.POINTER(i64), C.POINTER(i64)]
-    L.mhip_cns_accept_templates_ex.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_double, i32, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp),
-                                               C.POINTER(i64), C.POINTER(i64), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    pvp, pi64 = C.POINTER(vp), C.POINTER(i64)
+    cns_in, cns_out = [vp, vp, i32, i32, i32, C.c_double, i32], [pvp, pi64, pvp, pi64, pi64]      # the accept entry points: (cands .. threads), (accepted .. jobs)
+    L.mhip_cns_accept_templates.argtypes = [vp, vp, vp] + cns_in + cns_out
+    L.mhip_cns_accept_templates_ex.argtypes = [vp, vp] + cns_in + [i32] + cns_out + [pvp, pvp, pvp]
     L.mhip_debug_cns_table.argtypes = [vp, vp, i64, vp, vp, vp, i32, vp, i32, vp, vp]
-    L.mhip_cns_accept_templates_plan.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_double, i32, i32, i32, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp),
-                                                 C.POINTER(i64), C.POINTER(i64), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
-                                                 C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(vp)]
+    L.mhip_cns_accept_templates_plan.argtypes = [vp, vp] + cns_in + [i32, i32, i32] + cns_out + [pvp, pvp, pvp, pvp, pvp, pvp, pi64, pvp, pvp]
     L.mhip_debug_cns_plan.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(vp),
                                       C.POINTER(vp)]
-    L.mhip_cns_accept_templates_pieces.argtypes = L.mhip_cns_accept_templates_plan.argtypes + [C.POINTER(vp), C.POINTER(vp)]
+    L.mhip_cns_accept_templates_pieces.argtypes = L.mhip_cns_accept_templates_plan.argtypes + [pvp, pvp]
     L.mhip_debug_cns_pieces.argtypes = [vp, vp, i64, vp, vp, vp, vp, i32, vp, i32, C.POINTER(vp), C.POINTER(vp)]
-    L.mhip_cns_accept_templates_poa.argtypes = L.mhip_cns_accept_templates_pieces.argtypes + [C.POINTER(vp), C.POINTER(vp)]
+    L.mhip_cns_accept_templates_poa.argtypes = L.mhip_cns_accept_templates_pieces.argtypes + [pvp, pvp]
     L.mhip_debug_cns_poa.argtypes = [vp, vp, i64, vp, vp, vp, vp, i32, vp, i32, C.POINTER(vp), C.POINTER(vp)]
     L.mhip_cns_poa_small_words.restype = i64
     L.mhip_cns_poa_small_words.argtypes = []
@@ -455,24 +453,8 @@ assert EXT_CAND_DTYPE.itemsize == 52 and ACCEPTED_DTYPE.itemsize == 48
 def cns_accept_templates(ctx, vol, host_pac, cands, tmpl_begin, tech, min_align_size, min_mapping_ratio, threads=8):
     """mecat2cns' accept loop for a batch of templates.  cands: [n] EXT_CAND_DTYPE (or [n, 13] int32) grouped by template, sorted in
     place.  -> (accepted [k] ACCEPTED_DTYPE, strings as a uint8 array over the library's buffer, number of alignments computed)"""
-    cands = np.ascontiguousarray(cands)
-    tb = np.ascontiguousarray(tmpl_begin, dtype=np.int64)
     # (host_pac is no longer read by the library: the strings are built on the device; kept in the signature)
-    pac = np.ascontiguousarray(host_pac, dtype=np.uint8) if host_pac is not None else None
-    acc, st = C.c_void_p(), C.c_void_p()
-    na, sb, nj = C.c_int64(), C.c_int64(), C.c_int64()
-    _chk(lib().mhip_cns_accept_templates(ctx.h, vol.h, pac.ctypes.data if pac is not None else None, cands.ctypes.data, tb.ctypes.data, len(tb) - 1, tech, min_align_size,
-                                         float(min_mapping_ratio), threads, C.byref(acc), C.byref(na), C.byref(st), C.byref(sb), C.byref(nj)))
-    a = np.ctypeslib.as_array(C.cast(acc, C.POINTER(C.c_uint8)), shape=(na.value * 48,)).view(ACCEPTED_DTYPE).copy() if na.value else np.zeros(0, ACCEPTED_DTYPE)
-    lib().mhip_cns_free(acc)
-    if not sb.value:
-        lib().mhip_cns_free(st)
-        return a, np.zeros(0, np.uint8), nj.value
-    # the strings stay where the library put them (a gigabyte at config 2: no copy): a uint8 array over the C buffer, freed with the array
-    import weakref
-    s = np.ctypeslib.as_array(C.cast(st, C.POINTER(C.c_uint8)), shape=(sb.value,))
-    weakref.finalize(s, lib().mhip_cns_free, C.c_void_p(st.value))
-    return a, s, nj.value
+    return _cns_accept("", ctx, vol, cands, tmpl_begin, tech, min_align_size, min_mapping_ratio, CNS_WANT_STRINGS, threads=threads)[:3]
 
 
 CNS_WANT_STRINGS, CNS_WANT_TABLE = 1, 2
@@ -497,22 +479,7 @@ def cns_accept_templates_ex(ctx, vol, cands, tmpl_begin, tech, min_align_size, m
     -> (accepted, strings, number of alignments computed, table [TABLE_DTYPE], ident [uint8], table_begin [templates + 1]): template t
     owns table[table_begin[t]: table_begin[t + 1]], one item per base of the read.  Without CNS_WANT_STRINGS `strings` is empty and every
     str_offset -1; without CNS_WANT_TABLE the last three are empty."""
-    cands = np.ascontiguousarray(cands)
-    tb = np.ascontiguousarray(tmpl_begin, dtype=np.int64)
-    acc, st, tab, idn, tbeg = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-    na, sb, nj = C.c_int64(), C.c_int64(), C.c_int64()
-    _chk(lib().mhip_cns_accept_templates_ex(ctx.h, vol.h, cands.ctypes.data, tb.ctypes.data, len(tb) - 1, tech, min_align_size, float(min_mapping_ratio), threads,
-                                            int(want), C.byref(acc), C.byref(na), C.byref(st), C.byref(sb), C.byref(nj), C.byref(tab), C.byref(idn), C.byref(tbeg)))
-    a = np.ctypeslib.as_array(C.cast(acc, C.POINTER(C.c_uint8)), shape=(na.value * 48,)).view(ACCEPTED_DTYPE).copy() if na.value else np.zeros(0, ACCEPTED_DTYPE)
-    lib().mhip_cns_free(acc)
-    s = _cns_buffer(st, sb.value)
-    if tbeg.value:
-        begin = np.ctypeslib.as_array(C.cast(tbeg, C.POINTER(C.c_int64)), shape=(len(tb),)).copy()
-        lib().mhip_cns_free(tbeg)
-    else:
-        begin = np.zeros(0, np.int64)
-    nw = int(begin[-1]) if len(begin) else 0
-    return a, s, nj.value, _cns_buffer(tab, 4 * nw).view(TABLE_DTYPE), _cns_buffer(idn, nw), begin
+    return _cns_accept("_ex", ctx, vol, cands, tmpl_begin, tech, min_align_size, min_mapping_ratio, want, threads=threads)[:6]
 
 
 def debug_cns_table(ctx, buf, off, lens, soff, tmpl_letters):
@@ -561,6 +528,36 @@ def _cns_plan_out(seg, segb, win, nwin, er, erb, ntmpl):
                 eranges=_cns_take(er, np.int32, 2 * ner).reshape(-1, 2), erange_begin=erange_begin)
 
 
+def _cns_accept(entry, ctx, vol, cands, tmpl_begin, tech, min_align_size, min_mapping_ratio, want, min_cov=None, min_size=None, threads=8):
+    """the body of the five cns_accept_templates* bindings: mhip_cns_accept_templates + entry ("", "_ex", "_plan", "_pieces", "_poa"), which
+    decides the out-parameters behind out_jobs.  -> (accepted, strings, jobs, table, ident, table_begin, plan dict or None)"""
+    cands = np.ascontiguousarray(cands)
+    tb = np.ascontiguousarray(tmpl_begin, dtype=np.int64)
+    want = int(want)
+    acc, st, tab, idn, tbeg, seg, segb, win, er, erb, pc, pcb, cn, cnb = (C.c_void_p() for _ in range(14))
+    na, sb, nj, nwin = (C.c_int64() for _ in range(4))
+    outs = [acc, na, st, sb, nj] + [tab, idn, tbeg, seg, segb, win, nwin, er, erb, pc, pcb, cn, cnb][: {"": 0, "_ex": 3, "_plan": 9, "_pieces": 11, "_poa": 13}[entry]]
+    args = [cands.ctypes.data, tb.ctypes.data, len(tb) - 1, tech, min_align_size, float(min_mapping_ratio), threads]
+    if entry:
+        args += [want] if min_cov is None else [want, int(min_cov), int(min_size)]
+    else:
+        args.insert(0, None)          # host_pac
+    _chk(getattr(lib(), "mhip_cns_accept_templates" + entry)(ctx.h, vol.h, *args, *(C.byref(o) for o in outs)))
+    a = _cns_take(acc, ACCEPTED_DTYPE, na.value)
+    s = _cns_buffer(st, sb.value)              # the strings stay where the library put them (gigabytes at config 2: no copy)
+    begin = _cns_take(tbeg, np.int64, len(tb))
+    nw = int(begin[-1]) if len(begin) else 0
+    plan = _cns_plan_out(seg, segb, win, nwin, er, erb, len(tb) - 1) if want & CNS_WANT_PLAN else None
+    if plan is not None and want & CNS_WANT_PIECES:
+        plan["piece_begin"] = _cns_take(pcb, np.int64, int(nwin.value) + 1)
+        npc = int(plan["piece_begin"][-1]) if len(plan["piece_begin"]) else 0
+        plan["pieces"] = _cns_buffer(pc, npc * PIECE_DTYPE.itemsize).view(PIECE_DTYPE)
+    if plan is not None and want & CNS_WANT_POA:
+        plan["cns_begin"] = _cns_take(cnb, np.int64, int(nwin.value) + 1)
+        plan["cns"] = _cns_buffer(cn, int(plan["cns_begin"][-1]) if len(plan["cns_begin"]) else 0)
+    return a, s, nj.value, _cns_buffer(tab, 4 * nw).view(TABLE_DTYPE), _cns_buffer(idn, nw), begin, plan
+
+
 def cns_accept_templates_plan(ctx, vol, cands, tmpl_begin, tech, min_align_size, min_mapping_ratio, want, min_cov, min_size, threads=8):
     """cns_accept_templates_ex with CNS_WANT_PLAN allowed in `want`: the consensus plan of every template, computed on the device behind
     its table — effective ranges (get_effective_ranges), the segments consensus_worker would correct (runs of mat_cnt + ins_cnt >= min_cov
@@ -570,20 +567,7 @@ def cns_accept_templates_plan(ctx, vol, cands, tmpl_begin, tech, min_align_size,
     seg_begin [templates + 1], windows [WINDOW_DTYPE] in segment order then ascending sb (segment s owns windows[win_begin: win_end]),
     eranges [k, 2], erange_begin [templates + 1]; None without CNS_WANT_PLAN.  With CNS_WANT_PLAN alone neither strings nor tables are
     copied from the device."""
-    cands = np.ascontiguousarray(cands)
-    tb = np.ascontiguousarray(tmpl_begin, dtype=np.int64)
-    acc, st, tab, idn, tbeg = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-    seg, segb, win, er, erb = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-    na, sb, nj, nwin = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
-    _chk(lib().mhip_cns_accept_templates_plan(ctx.h, vol.h, cands.ctypes.data, tb.ctypes.data, len(tb) - 1, tech, min_align_size, float(min_mapping_ratio), threads,
-                                              int(want), int(min_cov), int(min_size), C.byref(acc), C.byref(na), C.byref(st), C.byref(sb), C.byref(nj), C.byref(tab),
-                                              C.byref(idn), C.byref(tbeg), C.byref(seg), C.byref(segb), C.byref(win), C.byref(nwin), C.byref(er), C.byref(erb)))
-    a = _cns_take(acc, ACCEPTED_DTYPE, na.value)
-    s = _cns_buffer(st, sb.value)
-    begin = _cns_take(tbeg, np.int64, len(tb))
-    nw = int(begin[-1]) if len(begin) else 0
-    plan = _cns_plan_out(seg, segb, win, nwin, er, erb, len(tb) - 1) if int(want) & CNS_WANT_PLAN else None
-    return a, s, nj.value, _cns_buffer(tab, 4 * nw).view(TABLE_DTYPE), _cns_buffer(idn, nw), begin, plan
+    return _cns_accept("_plan", ctx, vol, cands, tmpl_begin, tech, min_align_size, min_mapping_ratio, want, min_cov, min_size, threads)
 
 
 def debug_cns_plan(ctx, table, ident, table_begin, ranges, range_begin, tech, min_cov, min_size):
@@ -615,42 +599,27 @@ def cns_accept_templates_pieces(ctx, vol, cands, tmpl_begin, tech, min_align_siz
     piece_begin[w + 1]], ascending `aln` (index into `accepted`).  A piece's substrings are qaln[col: col + ncols] and saln[col: col + ncols]
     of that record; the reference feeds them to the graph with addAln(qstr, tstr, sb_out - sb + 1).  Without CNS_WANT_PIECES the result
     is cns_accept_templates_plan's.  With CNS_WANT_PLAN | CNS_WANT_PIECES alone neither strings nor tables are copied from the device."""
-    cands = np.ascontiguousarray(cands)
-    tb = np.ascontiguousarray(tmpl_begin, dtype=np.int64)
-    acc, st, tab, idn, tbeg = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-    seg, segb, win, er, erb, pc, pcb = (C.c_void_p() for _ in range(7))
-    na, sb, nj, nwin = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
-    _chk(lib().mhip_cns_accept_templates_pieces(ctx.h, vol.h, cands.ctypes.data, tb.ctypes.data, len(tb) - 1, tech, min_align_size, float(min_mapping_ratio), threads,
-                                                int(want), int(min_cov), int(min_size), C.byref(acc), C.byref(na), C.byref(st), C.byref(sb), C.byref(nj), C.byref(tab),
-                                                C.byref(idn), C.byref(tbeg), C.byref(seg), C.byref(segb), C.byref(win), C.byref(nwin), C.byref(er), C.byref(erb),
-                                                C.byref(pc), C.byref(pcb)))
-    a = _cns_take(acc, ACCEPTED_DTYPE, na.value)
-    s = _cns_buffer(st, sb.value)
-    begin = _cns_take(tbeg, np.int64, len(tb))
-    nw = int(begin[-1]) if len(begin) else 0
-    plan = _cns_plan_out(seg, segb, win, nwin, er, erb, len(tb) - 1) if int(want) & CNS_WANT_PLAN else None
-    if plan is not None and int(want) & CNS_WANT_PIECES:
-        plan["piece_begin"] = _cns_take(pcb, np.int64, int(nwin.value) + 1)
-        npc = int(plan["piece_begin"][-1]) if len(plan["piece_begin"]) else 0
-        plan["pieces"] = _cns_buffer(pc, npc * PIECE_DTYPE.itemsize).view(PIECE_DTYPE)
-    return a, s, nj.value, _cns_buffer(tab, 4 * nw).view(TABLE_DTYPE), _cns_buffer(idn, nw), begin, plan
+    return _cns_accept("_pieces", ctx, vol, cands, tmpl_begin, tech, min_align_size, min_mapping_ratio, want, min_cov, min_size, threads)
+
+
+def _cns_pairs_args(buf, off, lens, soff, send, windows, wstride):
+    """-> (debug_cns_pieces' and debug_cns_poa's arguments behind the context, the arrays they point into)"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    lens, soff, send = (np.ascontiguousarray(x, dtype=np.int32) for x in (lens, soff, send))
+    win = np.ascontiguousarray(windows, dtype=np.int32).reshape(-1, wstride)
+    assert len(off) == len(lens) == len(soff) == len(send)
+    return [buf.ctypes.data, len(buf), off.ctypes.data, lens.ctypes.data, soff.ctypes.data, send.ctypes.data, len(off), win.ctypes.data, len(win)], (buf, off, lens, soff, send, win)
 
 
 def debug_cns_pieces(ctx, buf, off, lens, soff, send, windows):
     """test hook: the piece kernels on one template.  buf: uint8 buffer, pair p = qaln at off[p] (lens[p] characters + NUL), saln right
     behind it, with soff[p] / send[p]; windows [k, 2] int32 (sb, se), ascending and disjoint.  -> (pieces [PIECE_DTYPE], piece_begin
     [k + 1]); `aln` is the pair's number"""
-    buf = np.ascontiguousarray(buf, dtype=np.uint8)
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    lens = np.ascontiguousarray(lens, dtype=np.int32)
-    soff = np.ascontiguousarray(soff, dtype=np.int32)
-    send = np.ascontiguousarray(send, dtype=np.int32)
-    win = np.ascontiguousarray(windows, dtype=np.int32).reshape(-1, 2)
-    assert len(off) == len(lens) == len(soff) == len(send)
+    args, keep = _cns_pairs_args(buf, off, lens, soff, send, windows, 2)
     pc, pcb = C.c_void_p(), C.c_void_p()
-    _chk(lib().mhip_debug_cns_pieces(ctx.h, buf.ctypes.data, len(buf), off.ctypes.data, lens.ctypes.data, soff.ctypes.data, send.ctypes.data, len(off), win.ctypes.data,
-                                     len(win), C.byref(pc), C.byref(pcb)))
-    piece_begin = _cns_take(pcb, np.int64, len(win) + 1)
+    _chk(lib().mhip_debug_cns_pieces(ctx.h, *args, C.byref(pc), C.byref(pcb)))
+    piece_begin = _cns_take(pcb, np.int64, len(keep[-1]) + 1)
     return _cns_take(pc, PIECE_DTYPE, int(piece_begin[-1])), piece_begin
 
 
@@ -668,44 +637,16 @@ def cns_accept_templates_poa(ctx, vol, cands, tmpl_begin, tech, min_align_size, 
     (int)(cov * 0.4)).  The plan dict gets two more entries: cns [uint8] and cns_begin [windows + 1]; window w owns cns[cns_begin[w]:
     cns_begin[w + 1]], both end letters included.  Without CNS_WANT_POA the result is cns_accept_templates_pieces'.  The pieces are
     copied from the device only with CNS_WANT_PIECES; CNS_WANT_PLAN | CNS_WANT_POA alone copies no strings, tables or pieces."""
-    cands = np.ascontiguousarray(cands)
-    tb = np.ascontiguousarray(tmpl_begin, dtype=np.int64)
-    acc, st, tab, idn, tbeg = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-    seg, segb, win, er, erb, pc, pcb, cn, cnb = (C.c_void_p() for _ in range(9))
-    na, sb, nj, nwin = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
-    _chk(lib().mhip_cns_accept_templates_poa(ctx.h, vol.h, cands.ctypes.data, tb.ctypes.data, len(tb) - 1, tech, min_align_size, float(min_mapping_ratio), threads,
-                                             int(want), int(min_cov), int(min_size), C.byref(acc), C.byref(na), C.byref(st), C.byref(sb), C.byref(nj), C.byref(tab),
-                                             C.byref(idn), C.byref(tbeg), C.byref(seg), C.byref(segb), C.byref(win), C.byref(nwin), C.byref(er), C.byref(erb),
-                                             C.byref(pc), C.byref(pcb), C.byref(cn), C.byref(cnb)))
-    a = _cns_take(acc, ACCEPTED_DTYPE, na.value)
-    s = _cns_buffer(st, sb.value)
-    begin = _cns_take(tbeg, np.int64, len(tb))
-    nw = int(begin[-1]) if len(begin) else 0
-    plan = _cns_plan_out(seg, segb, win, nwin, er, erb, len(tb) - 1) if int(want) & CNS_WANT_PLAN else None
-    if plan is not None and int(want) & CNS_WANT_PIECES:
-        plan["piece_begin"] = _cns_take(pcb, np.int64, int(nwin.value) + 1)
-        npc = int(plan["piece_begin"][-1]) if len(plan["piece_begin"]) else 0
-        plan["pieces"] = _cns_buffer(pc, npc * PIECE_DTYPE.itemsize).view(PIECE_DTYPE)
-    if plan is not None and int(want) & CNS_WANT_POA:
-        plan["cns_begin"] = _cns_take(cnb, np.int64, int(nwin.value) + 1)
-        plan["cns"] = _cns_buffer(cn, int(plan["cns_begin"][-1]) if len(plan["cns_begin"]) else 0)
-    return a, s, nj.value, _cns_buffer(tab, 4 * nw).view(TABLE_DTYPE), _cns_buffer(idn, nw), begin, plan
+    return _cns_accept("_poa", ctx, vol, cands, tmpl_begin, tech, min_align_size, min_mapping_ratio, want, min_cov, min_size, threads)
 
 
 def debug_cns_poa(ctx, buf, off, lens, soff, send, windows):
     """test hook: the piece kernels and then the POA kernels on one template.  debug_cns_pieces' arguments with windows [k, 3] int32
     (sb, se, cov).  -> (cns [uint8], cns_begin [k + 1])"""
-    buf = np.ascontiguousarray(buf, dtype=np.uint8)
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    lens = np.ascontiguousarray(lens, dtype=np.int32)
-    soff = np.ascontiguousarray(soff, dtype=np.int32)
-    send = np.ascontiguousarray(send, dtype=np.int32)
-    win = np.ascontiguousarray(windows, dtype=np.int32).reshape(-1, 3)
-    assert len(off) == len(lens) == len(soff) == len(send)
+    args, keep = _cns_pairs_args(buf, off, lens, soff, send, windows, 3)
     cn, cnb = C.c_void_p(), C.c_void_p()
-    _chk(lib().mhip_debug_cns_poa(ctx.h, buf.ctypes.data, len(buf), off.ctypes.data, lens.ctypes.data, soff.ctypes.data, send.ctypes.data, len(off), win.ctypes.data,
-                                  len(win), C.byref(cn), C.byref(cnb)))
-    cns_begin = _cns_take(cnb, np.int64, len(win) + 1)
+    _chk(lib().mhip_debug_cns_poa(ctx.h, *args, C.byref(cn), C.byref(cnb)))
+    cns_begin = _cns_take(cnb, np.int64, len(keep[-1]) + 1)
     return _cns_take(cn, np.uint8, int(cns_begin[-1])), cns_begin
 
 

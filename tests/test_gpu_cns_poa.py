@@ -235,6 +235,31 @@ def test_slices_and_templates_without_work(ctx, monkeypatch):
     assert len(acc) == 0 and nj > 0 and len(p["windows"]) == 0 and len(p["cns"]) == 0 and p["cns_begin"].tolist() == [0]
 
 
+def test_slice_kinds_at_the_hand_over(ctx, monkeypatch):
+    """every template a slice of its own: slices with windows, slices with a table and no window, and a template without candidates
+    between them, put together at the hand-over — byte for byte what the batch gives in one slice"""
+    import mecat_amd.hip as M
+    S, TB, PL, PC, PO = M.CNS_WANT_STRINGS, M.CNS_WANT_TABLE, M.CNS_WANT_PLAN, M.CNS_WANT_PIECES, M.CNS_WANT_POA
+    g = golden_set("pacbio", 12)
+    tb = np.concatenate([g["tb"][:7], g["tb"][6:]])          # template 6 has no candidates
+    kw = dict(tb=tb, ratio=1.0, params=(4, 3000))            # the mapping ratio leaves some templates too few alignments for a segment
+    wants = (PL | PO, PL | PC, S | TB | PL | PC | PO)
+    one = {w: run(ctx, g, w, **kw) for w in wants}
+    p, begin = one[wants[2]][6], one[wants[2]][5]
+    seg, sb = p["segments"], p["seg_begin"]
+    nwin = np.array([int((seg["win_end"][sb[t]: sb[t + 1]] - seg["win_begin"][sb[t]: sb[t + 1]]).sum()) for t in range(len(tb) - 1)])
+    has_table = np.diff(begin) > 0
+    assert int((has_table & (nwin == 0)).sum()) >= 1 and int((nwin > 0).sum()) >= 2 and not has_table[6] and nwin.sum() == len(p["windows"])
+    monkeypatch.setenv("MECAT_CNS_SLICE_JOBS", "1")
+    for w in wants:
+        x, y = one[w], run(ctx, g, w, **kw)
+        assert x[2] == y[2] and all(np.asarray(a).tobytes() == np.asarray(b).tobytes() for a, b in zip(x[:2] + x[3:6], y[:2] + y[3:6]))
+        assert sorted(x[6]) == sorted(y[6]) and ("pieces" in x[6]) == bool(w & PC) and ("cns" in x[6]) == bool(w & PO)
+        for k in x[6]:
+            assert x[6][k].tobytes() == y[6][k].tobytes(), (w, k)
+    assert len(one[wants[2]][1]) > 0 and len(p["pieces"]) > 0 and len(p["cns"]) > 0
+
+
 def test_refusals(ctx):
     import mecat_amd.hip as M
     S, TB, PL, PC, PO = M.CNS_WANT_STRINGS, M.CNS_WANT_TABLE, M.CNS_WANT_PLAN, M.CNS_WANT_PIECES, M.CNS_WANT_POA
