@@ -434,6 +434,9 @@ int  mhip_debug_cns_plan(mhip_ctx* ctx, const mhip_cns_table_item* table, const 
                          const int32_t* ranges, const int64_t* range_begin, int tech, int min_cov, int min_size,
                          mhip_cns_segment** out_segments, int64_t** out_seg_begin, mhip_cns_window** out_windows, int64_t* out_n_windows,
                          int32_t** out_eranges, int64_t** out_erange_begin);
+/* test hook: the plan's prefix-sum kernel — the single-workgroup scan every stage's count-to-position kernel calls (csrc/scan.h) — on a
+ * host array: out[i] = base + cnt[0] + .. + cnt[i - 1] for i <= n, summed in 64 bits.  Refused before anything is launched: n < 0. */
+int  mhip_debug_scan(mhip_ctx* ctx, const int32_t* cnt, int64_t n, int64_t base, int64_t* out /* [n + 1] */);
 /* ---- the POA windows' substrings (cns_pieces.hip).  For a listed window (sb, se) the reference's meap_cns_one_indel
  * (mecat_correction.cpp:62-78) asks every accepted alignment of the template, in add order, for its part of the window:
  * CnsAln::retrieve_aln_subseqs (reads_correction_aux.h:47-68), a cursor per alignment that only moves forward, and feeds each pair of

@@ -37,6 +37,7 @@
 
 #include "common.h"
 #include "cns_fwd.h"
+#include "scan.h"
 
 #define AL_BLOCK 256
 #define AL_WAVES (AL_BLOCK / WAVE)
@@ -1174,29 +1175,9 @@ __global__ void dw_stitch(const mhip_aln_job* __restrict__ jobs, const DirResult
 // over 1024-read tiles), then one thread per (read, slot).
 __global__ __launch_bounds__(1024) void dw_job_scan(const int32_t* __restrict__ counts, int n_reads, int part_index, int part_count,
                                                     unsigned int* __restrict__ first, int* __restrict__ num_jobs) {
-    __shared__ unsigned int wtot[16];
-    __shared__ unsigned int carry_all;
-    if (threadIdx.x == 0) carry_all = 0;
-    __syncthreads();
-    for (int t0 = 0; t0 < n_reads; t0 += 1024) {
-        const int i = t0 + threadIdx.x;
-        const unsigned int c = i < n_reads ? (unsigned int)counts[i] : 0u;
-        unsigned int incl = c;
-        for (int o = 1; o < 64; o <<= 1) {
-            unsigned int v = __shfl_up(incl, o);
-            if (lane_id() >= o) incl += v;
-        }
-        if (lane_id() == 63) wtot[threadIdx.x >> 6] = incl;
-        __syncthreads();
-        unsigned int base = carry_all;
-        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) base += wtot[w];
-        if (i < n_reads) first[i] = base + incl - c;         // global index of this read's first candidate
-        __syncthreads();
-        if (threadIdx.x == 1023) carry_all = base + incl;
-        __syncthreads();
-    }
+    const unsigned int tot = scan_array_1024<unsigned int>(      // first[i]: global index of read i's first candidate
+        n_reads, 0u, [&](long long i) { return (unsigned int)counts[i]; }, [&](long long i, unsigned int p) { first[i] = p; });
     if (threadIdx.x == 0) {
-        const unsigned int tot = carry_all;
         unsigned int mine = tot;
         if (part_count > 1) mine = tot / (unsigned)part_count + ((unsigned)part_index < tot % (unsigned)part_count ? 1u : 0u);
         *num_jobs = (int)mine;

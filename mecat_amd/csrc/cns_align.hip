@@ -18,6 +18,7 @@
 
 #include "cns_fwd.h"
 #include "dw_helpers.h"
+#include "scan.h"
 
 #define CN_BLOCK 256
 #define CN_WAVES (CN_BLOCK / WAVE)
@@ -348,28 +349,9 @@ __global__ __launch_bounds__(1024) void cns_scan(const uint32_t* __restrict__ ca
     caps += (size_t)blockIdx.x * (size_t)m;            // workgroup b: array b of m counts -> array b of m + 1 positions, total[b]
     out += (size_t)blockIdx.x * ((size_t)m + 1);
     total += blockIdx.x;
-    __shared__ unsigned long long wsum[16];
-    __shared__ unsigned long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int t0 = 0; t0 < m; t0 += 1024) {
-        const int i = t0 + (int)threadIdx.x;
-        const unsigned long long w = i < m ? (unsigned long long)caps[i] : 0ull;
-        unsigned long long incl = w;
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long v = __shfl_up(incl, o);
-            if ((int)(threadIdx.x & 63) >= o) incl += v;
-        }
-        if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-        __syncthreads();
-        unsigned long long before = carry;
-        for (int k = 0; k < (int)(threadIdx.x >> 6); ++k) before += wsum[k];
-        if (i < m) out[i] = (uint32_t)(before + incl - w);
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = before + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { out[m] = (uint32_t)carry; *total = carry; }
+    const unsigned long long sum = scan_array_1024<unsigned long long>(      // summed in 64 bits, stored in 32
+        m, 0ull, [&](long long i) { return caps[i]; }, [&](long long i, unsigned long long p) { out[i] = (uint32_t)p; });
+    if (threadIdx.x == 0) { out[m] = (uint32_t)sum; *total = sum; }
 }
 
 // cns_trace — one LANE per block record.  Backwards over the block's row records from its end cell: bit (k - min_k) / 2 of a row says
@@ -684,28 +666,9 @@ namespace {
 
 // exclusive prefix over the directions' word counts (ceil(cols / 16)); one block, the total behind the last entry
 __global__ __launch_bounds__(1024) void ae_word_offsets(const CnsDir* __restrict__ dres, int nd, unsigned long long* __restrict__ offs) {
-    __shared__ unsigned long long wsum[16];
-    __shared__ unsigned long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int t0 = 0; t0 < nd; t0 += 1024) {
-        const int i = t0 + (int)threadIdx.x;
-        const unsigned long long w = i < nd ? (unsigned long long)((dres[i].cols + 15) >> 4) : 0ull;
-        unsigned long long incl = w;
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long v = __shfl_up(incl, o);
-            if ((int)(threadIdx.x & 63) >= o) incl += v;
-        }
-        if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-        __syncthreads();
-        unsigned long long before = carry;
-        for (int k = 0; k < (int)(threadIdx.x >> 6); ++k) before += wsum[k];
-        if (i < nd) offs[i] = before + incl - w;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = before + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) offs[nd] = carry;
+    const unsigned long long total = scan_array_1024<unsigned long long>(
+        nd, 0ull, [&](long long i) { return (dres[i].cols + 15) >> 4; }, [&](long long i, unsigned long long p) { offs[i] = p; });
+    if (threadIdx.x == 0) offs[nd] = total;
 }
 
 // one wave per direction: its words from the fixed-stride array to their place in the dense one

@@ -39,6 +39,7 @@
 
 #include "common.h"
 #include "cns_pieces.h"
+#include "scan.h"
 
 static_assert(sizeof(mhip_cns_piece) == 16 && sizeof(CnsPieceItem) == 24, "piece records");
 
@@ -114,28 +115,7 @@ __global__ __launch_bounds__(256) void cns_pieces_range(const CnsPieceItem* __re
 
 // out[i] = cnt[0] + .. + cnt[i - 1] for i <= n, in 64 bits; *total = out[n].  One block of 1024.
 __global__ __launch_bounds__(1024) void cns_pieces_scan(const int32_t* __restrict__ cnt, long long n, long long* __restrict__ out, long long* __restrict__ total) {
-    __shared__ long long wsum[16];
-    const int lane = lane_id(), w = threadIdx.x >> 6;
-    long long run = 0;
-    for (long long i0 = 0; i0 < n; i0 += 1024) {
-        const long long i = i0 + threadIdx.x;
-        const long long v = i < n ? (long long)cnt[i] : 0;
-        long long x = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            const long long y = __shfl_up(x, o);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) wsum[w] = x;
-        __syncthreads();
-        long long off = run, tot = 0;
-        for (int k = 0; k < 16; ++k) {
-            if (k < w) off += wsum[k];
-            tot += wsum[k];
-        }
-        if (i < n) out[i] = off + x - v;
-        run += tot;
-        __syncthreads();
-    }
+    const long long run = scan_array_1024<long long>(n, 0, [&](long long i) { return cnt[i]; }, [&](long long i, long long p) { out[i] = p; });
     if (threadIdx.x == 0) {
         out[n] = run;
         if (total) *total = run;

@@ -39,6 +39,7 @@
 #include "common.h"
 #include "cns_plan.h"
 #include "cns_ranges.h"
+#include "scan.h"
 
 static double wall_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -102,29 +103,8 @@ __global__ __launch_bounds__(256) void cns_plan_segments(const uint32_t* __restr
 // One block of 1024.
 __global__ __launch_bounds__(1024) void cns_plan_scan(const int32_t* __restrict__ cnt, long long n, const long long* __restrict__ n_dev, long long n_base,
                                                       long long base, long long* __restrict__ out, long long* __restrict__ total) {
-    __shared__ long long wsum[16];
     if (n_dev) n = *n_dev - n_base;
-    const int lane = lane_id(), w = threadIdx.x >> 6;
-    long long run = base;
-    for (long long i0 = 0; i0 < n; i0 += 1024) {
-        const long long i = i0 + threadIdx.x;
-        const long long v = i < n ? (long long)cnt[i] : 0;
-        long long x = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            const long long y = __shfl_up(x, o);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) wsum[w] = x;
-        __syncthreads();
-        long long off = run, tot = 0;
-        for (int k = 0; k < 16; ++k) {
-            if (k < w) off += wsum[k];
-            tot += wsum[k];
-        }
-        if (i < n) out[i] = off + x - v;
-        run += tot;
-        __syncthreads();
-    }
+    const long long run = scan_array_1024<long long>(n, base, [&](long long i) { return cnt[i]; }, [&](long long i, long long p) { out[i] = p; });
     if (threadIdx.x == 0) {
         out[n] = run;
         if (total) *total = run;
@@ -281,6 +261,22 @@ int cns_plan_launch(mhip_ctx* c, int set, const uint32_t* d_table, const uint8_t
 }
 
 extern "C" {
+
+// TEST HOOK (tests/test_gpu_scan.py): cns_plan_scan — scan.h's routine with a base — on a host array, n from the host.
+int mhip_debug_scan(mhip_ctx* c, const int32_t* cnt, int64_t n, int64_t base, int64_t* out) {
+    HIPCHK(hipSetDevice(c->device));
+    if (n < 0 || !out || (n > 0 && !cnt)) { mhip_set_error("debug scan: n %lld, or a NULL array", (long long)n); return -1; }
+    int32_t* d_cnt;
+    long long* d_out;
+    if (c->scratch("ds_cnt", std::max<size_t>(sizeof(int32_t) * (size_t)n, 16), (void**)&d_cnt)) return -1;
+    if (c->scratch("ds_out", sizeof(long long) * ((size_t)n + 1), (void**)&d_out)) return -1;
+    if (n) HIPCHK(hipMemcpyAsync(d_cnt, cnt, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    LAUNCH(c, "cns_plan_scan", cns_plan_scan, 1, 1024, 0, d_cnt, (long long)n, (const long long*)nullptr, 0LL, (long long)base, d_out, (long long*)nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(long long) * ((size_t)n + 1), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
 
 // TEST HOOK (tests/test_gpu_cns_plan.py): cns_effective_ranges and the kernels above on host-supplied tables.  Template k owns
 // table / ident [table_begin[k], table_begin[k + 1]) and the mapping ranges (soff, send) ranges[2 * range_begin[k] .. 2 * range_begin[k + 1]).

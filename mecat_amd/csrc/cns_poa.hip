@@ -31,6 +31,7 @@
 #include "cns_pieces.h"
 #include "cns_poa.h"
 #include "cns_poa_dev.h"
+#include "scan.h"
 
 namespace {
 
@@ -88,29 +89,11 @@ __global__ __launch_bounds__(256) void cns_poa_bound(const mhip_cns_window* __re
 
 // out[i] = v[0] + .. + v[i - 1] for i <= n; IN PLACE is fine (out == v; then v needs n + 1 entries).  One block of 1024.  *vmax: the largest v
 __global__ __launch_bounds__(1024) void cns_poa_scan(const long long* v, long long n, long long* out, long long* __restrict__ total, long long* __restrict__ vmax) {
-    __shared__ long long wsum[16], wmax[16];
+    __shared__ long long wmax[16];
     const int lane = lane_id(), w = threadIdx.x >> 6;
-    long long run = 0, mx = 0;
-    for (long long i0 = 0; i0 < n; i0 += 1024) {
-        const long long i = i0 + threadIdx.x;
-        const long long x0 = i < n ? v[i] : 0;
-        long long x = x0;
-        mx = max(mx, x0);
-        for (int o = 1; o < 64; o <<= 1) {
-            const long long y = __shfl_up(x, o);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) wsum[w] = x;
-        __syncthreads();
-        long long off = run, tot = 0;
-        for (int k = 0; k < 16; ++k) {
-            if (k < w) off += wsum[k];
-            tot += wsum[k];
-        }
-        if (i < n) out[i] = off + x - x0;
-        run += tot;
-        __syncthreads();
-    }
+    long long mx = 0;
+    const long long run = scan_array_1024<long long>(
+        n, 0, [&](long long i) { const long long x = v[i]; mx = max(mx, x); return x; }, [&](long long i, long long p) { out[i] = p; });
     for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
     if (lane == 0) wmax[w] = mx;
     __syncthreads();

@@ -31,6 +31,7 @@
 
 #include "common.h"
 #include "index_part.h"
+#include "scan.h"
 
 int mhip_seed_reads_chunked_dev(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, int rid0, int chunk,
                                 int nranks, int n, const mhip_params* P, void* d_out, void* d_out_counts);
@@ -134,29 +135,11 @@ namespace {
 
 // one block per rank: exclusive prefix of its counts, total to totals[rank]
 __global__ __launch_bounds__(1024) void xg_prefix(const int32_t* __restrict__ cnt_all, int n_pad, uint32_t* __restrict__ pref, long long* __restrict__ totals) {
-    __shared__ unsigned int wtot[16];
-    __shared__ unsigned int carry;
     const int r = blockIdx.x;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int t0 = 0; t0 < n_pad; t0 += 1024) {
-        const int i = t0 + threadIdx.x;
-        const unsigned int c = i < n_pad ? (unsigned int)cnt_all[(size_t)r * n_pad + i] : 0u;
-        unsigned int incl = c;
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned int v = __shfl_up(incl, o);
-            if ((threadIdx.x & 63) >= (unsigned)o) incl += v;
-        }
-        if ((threadIdx.x & 63) == 63) wtot[threadIdx.x >> 6] = incl;
-        __syncthreads();
-        unsigned int base = carry;
-        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) base += wtot[w];
-        if (i < n_pad) pref[(size_t)r * n_pad + i] = base + incl - c;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = base + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) totals[r] = (long long)carry;
+    const int32_t* __restrict__ cnt = cnt_all + (size_t)r * n_pad;
+    uint32_t* __restrict__ row = pref + (size_t)r * n_pad;
+    const unsigned int total = scan_array_1024<unsigned int>(n_pad, 0u, [&](long long i) { return (unsigned int)cnt[i]; }, [&](long long i, unsigned int p) { row[i] = p; });
+    if (threadIdx.x == 0) totals[r] = (long long)total;
 }
 
 // this rank's occupied records, dense, local read-major
@@ -203,27 +186,7 @@ __global__ void xg_make_jobs(const mhip_candidate* __restrict__ cands, const int
 
 // exclusive scan of the read-major counts (one block)
 __global__ __launch_bounds__(1024) void xg_read_first(const int32_t* __restrict__ counts, int n, uint32_t* __restrict__ first) {
-    __shared__ unsigned int wtot[16];
-    __shared__ unsigned int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int t0 = 0; t0 < n; t0 += 1024) {
-        const int i = t0 + threadIdx.x;
-        const unsigned int c = i < n ? (unsigned int)counts[i] : 0u;
-        unsigned int incl = c;
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned int v = __shfl_up(incl, o);
-            if ((threadIdx.x & 63) >= (unsigned)o) incl += v;
-        }
-        if ((threadIdx.x & 63) == 63) wtot[threadIdx.x >> 6] = incl;
-        __syncthreads();
-        unsigned int base = carry;
-        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) base += wtot[w];
-        if (i < n) first[i] = base + incl - c;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = base + incl;
-        __syncthreads();
-    }
+    scan_array_1024<unsigned int>(n, 0u, [&](long long i) { return (unsigned int)counts[i]; }, [&](long long i, unsigned int p) { first[i] = p; });
 }
 
 // dense rank-major results -> dense read-major results

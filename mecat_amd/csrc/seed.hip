@@ -41,6 +41,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "scan.h"
 
 #define SEED_BLOCK 256
 #define SEED_WAVES (SEED_BLOCK / WAVE)
@@ -186,28 +187,8 @@ __global__ __launch_bounds__(SEED_BLOCK) void seed_probe(const uint32_t* __restr
 
 // exclusive scan of strand_hits[ns] -> hit_base[ns + 1] (single block, sequential over tiles)
 __global__ __launch_bounds__(1024) void seed_scan(const uint32_t* __restrict__ hits, int ns, uint64_t* __restrict__ base) {
-    __shared__ uint64_t wtot[16];
-    __shared__ uint64_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int t0 = 0; t0 < ns; t0 += 1024) {
-        int i = t0 + threadIdx.x;
-        uint64_t v = i < ns ? hits[i] : 0;
-        uint64_t incl = v;
-        for (int o = 1; o < 64; o <<= 1) {
-            uint64_t n = __shfl_up(incl, o);
-            if (lane_id() >= o) incl += n;
-        }
-        if (lane_id() == 63) wtot[threadIdx.x >> 6] = incl;
-        __syncthreads();
-        uint64_t b = carry;
-        for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) b += wtot[w];
-        if (i < ns) base[i] = b + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = b + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) base[ns] = carry;
+    const uint64_t total = scan_array_1024<uint64_t>(ns, 0, [&](long long i) { return hits[i]; }, [&](long long i, uint64_t p) { base[i] = p; });
+    if (threadIdx.x == 0) base[ns] = total;
 }
 
 // ------------------------------------------------------------------------------------------------ hit iteration

@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "scan.h"
 
 #define X_SEG 500
 #define X_MAXN 736                       // last block: one side < 600, the other <= 718 (gapalign.cpp:24-30)
@@ -951,27 +952,7 @@ __global__ __launch_bounds__(XO_THREADS) void xo_order_jobs(const mhip_aln_job* 
     }
 }
 __global__ __launch_bounds__(1024) void xo_scan(unsigned int* __restrict__ cnt, int m) {      // counts -> first positions, in place; one workgroup
-    __shared__ unsigned int wsum[16];
-    __shared__ unsigned int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int i0 = 0; i0 < m; i0 += 1024) {
-        const int i = i0 + (int)threadIdx.x;
-        const unsigned int c = i < m ? cnt[i] : 0u;
-        unsigned int incl = c;
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned int v = __shfl_up(incl, o);
-            if ((int)(threadIdx.x & 63) >= o) incl += v;
-        }
-        if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-        __syncthreads();
-        unsigned int before = carry;
-        for (int k = 0; k < (int)(threadIdx.x >> 6); ++k) before += wsum[k];
-        if (i < m) cnt[i] = before + incl - c;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = before + incl;
-        __syncthreads();
-    }
+    scan_array_1024<unsigned int>(m, 0u, [&](long long i) { return cnt[i]; }, [&](long long i, unsigned int p) { cnt[i] = p; });
 }
 
 // XdropAligner::go tail (xdrop_gapalign.cpp:396-438): the left half is emitted without its last column

@@ -128,6 +128,7 @@ def lib():
     L.mhip_cns_accept_templates_plan.argtypes = [vp, vp] + cns_in + [i32, i32, i32] + cns_out + [pvp, pvp, pvp, pvp, pvp, pvp, pi64, pvp, pvp]
     L.mhip_debug_cns_plan.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(vp),
                                       C.POINTER(vp)]
+    L.mhip_debug_scan.argtypes = [vp, vp, i64, i64, vp]
     L.mhip_cns_accept_templates_pieces.argtypes = L.mhip_cns_accept_templates_plan.argtypes + [pvp, pvp]
     L.mhip_debug_cns_pieces.argtypes = [vp, vp, i64, vp, vp, vp, vp, i32, vp, i32, C.POINTER(vp), C.POINTER(vp)]
     L.mhip_cns_accept_templates_poa.argtypes = L.mhip_cns_accept_templates_pieces.argtypes + [pvp, pvp]
@@ -585,6 +586,17 @@ def debug_cns_plan(ctx, table, ident, table_begin, ranges, range_begin, tech, mi
     _chk(lib().mhip_debug_cns_plan(ctx.h, table.ctypes.data, ident.ctypes.data, tbeg.ctypes.data, len(tbeg) - 1, rng.ctypes.data, rbeg.ctypes.data, int(tech),
                                    int(min_cov), int(min_size), C.byref(seg), C.byref(segb), C.byref(win), C.byref(nwin), C.byref(er), C.byref(erb)))
     return _cns_plan_out(seg, segb, win, nwin, er, erb, len(tbeg) - 1)
+
+
+def debug_scan(ctx, cnt, base=0, n=None):
+    """test hook: the single-workgroup scan (csrc/scan.h) through the plan's prefix-sum kernel.  cnt: int32 counts, n: how many of them
+    (all).  -> int64 [n + 1], out[i] = base + cnt[0] + .. + cnt[i - 1]"""
+    cnt = np.ascontiguousarray(cnt, dtype=np.int32)
+    n = len(cnt) if n is None else int(n)
+    assert n <= len(cnt)
+    out = np.empty(max(n, 0) + 1, np.int64)
+    _chk(lib().mhip_debug_scan(ctx.h, cnt.ctypes.data, n, int(base), out.ctypes.data))
+    return out
 
 
 CNS_WANT_PIECES = 8

@@ -93,6 +93,20 @@ def test_hook_width(ctx):
         hook(ctx, alns + [alns[0]], [(50, 60)])
 
 
+@pytest.mark.parametrize("nwin", [1023, 1024, 1025, 2049])
+def test_hook_window_counts_across_the_scan_tiles(ctx, nwin):
+    """cns_pieces_scan turns the windows' piece counts into piece_begin, 1 024 windows a tile with a running sum: window lists that end
+    one short of a tile, on it, one behind it and one behind the second — a window on every other position, three alignments that each
+    cover a part of the template, so the counts are 1 .. 3 and change along the list"""
+    rng = np.random.default_rng(nwin)
+    letters = lambda n: "".join(rng.choice(list("ACGT"), n))
+    L = 2 * nwin + 1
+    alns = [K.aln(letters(L), 0), K.aln(letters(L - 700), 300), K.aln(letters(500) + "--" + letters(900), 1100)]
+    got = check(ctx, alns, [(2 * w, 2 * w + 1) for w in range(nwin)])
+    cnt = np.diff(got[1])
+    assert len(cnt) == nwin and cnt.min() >= 1 and cnt.max() == 3 and got[1][-1] == len(got[0]) > nwin
+
+
 def test_hook_random(ctx):
     """250 seeded templates of up to 2 000 positions and up to 40 alignments, gap runs of up to 70 columns, random window lists"""
     rng = np.random.default_rng(20262)
