@@ -59,14 +59,24 @@ def test_cli_default_task_is_align_and_small_slabs(tmp_path):
 
 
 def test_cli_resume_skips_finished_volume(tmp_path):
+    """a finished row is not computed again; the split is still redone, and its volume file — written on a thread of its own in a
+    one-process run — is complete when the process has left (the working directory is given relative to the process's own directory,
+    the same name in both runs: fileindex.txt holds the volume files' names as given)"""
     fa = _fasta(tmp_path, "tiny")
     wrk = tmp_path / "w_resume"
     wrk.mkdir()
     (wrk / "r_0").write_text("sentinel\n")
     out = str(tmp_path / "r.can")
-    r = subprocess.run([BIN, "-j", "0", "-d", fa, "-o", out, "-w", str(wrk)], capture_output=True, text=True)
+    r = subprocess.run([BIN, "-j", "0", "-d", fa, "-o", out, "-w", "w_resume"], capture_output=True, text=True, cwd=str(tmp_path))
     assert r.returncode == 0 and "volume 0 has been finished" in r.stderr
     assert open(out).read() == "sentinel\n"
+    fresh = tmp_path / "fresh"
+    fresh.mkdir()
+    r = subprocess.run([BIN, "-j", "0", "-d", fa, "-o", str(fresh / "f.can"), "-w", "w_resume"], capture_output=True, text=True, cwd=str(fresh))
+    assert r.returncode == 0, r.stderr[-2000:]
+    for name in ("vol0", "fileindex.txt"):
+        assert (wrk / name).read_bytes() == (fresh / "w_resume" / name).read_bytes(), name
+    assert len((wrk / "vol0").read_bytes()) > 100000
 
 
 def test_cli_multi_volume_grid(tmp_path):
@@ -123,6 +133,12 @@ def test_cli_multi_volume_grid(tmp_path):
             assert outs[0] == got
 
 
+def _rank_files(wrk):
+    """heartbeat files (rank_<r>.alive.<token>) and failure markers (rank_<r>.failed.<token>) in a working directory"""
+    import fnmatch
+    return sorted(f for f in os.listdir(wrk) if fnmatch.fnmatch(f, "rank_*.alive.*") or fnmatch.fnmatch(f, "rank_*.failed.*"))
+
+
 @pytest.mark.parametrize("task", ["0", "1"])
 def test_cli_two_processes_share_the_grid_rows(tmp_path, task):
     """multi-GPU mode of the driver: two processes (here both on GPU 0) deal out the rows of a 3-volume grid; the merged
@@ -145,6 +161,7 @@ def test_cli_two_processes_share_the_grid_rows(tmp_path, task):
     assert open(two).read() == open(one).read()
     assert len(open(two).read().splitlines()) > 300
     assert sorted(f for f in os.listdir(wrk) if f.startswith("r_")) == ["r_0", "r_1", "r_2"]
+    assert _rank_files(wrk) == []          # every rank, rank 0 included, has stopped its heartbeat and removed the file; none failed
 
 
 @pytest.mark.parametrize("task,nproc,vols,ishard", [("0", 2, 1, "1"), ("1", 2, 1, "0"), ("1", 3, 3, "1"), ("0", 2, 3, "0")])
@@ -183,6 +200,7 @@ def test_cli_processes_share_the_grid_cells(tmp_path, task, nproc, vols, ishard)
     assert sorted(open(many).read().splitlines()) == sorted(open(one).read().splitlines())
     assert len(open(many).read().splitlines()) > (5000 if vols == 1 else 300)
     assert sorted(f for f in os.listdir(wrk) if f.startswith("r_")) == ["r_%d" % i for i in range(vols)]      # no part files left behind
+    assert _rank_files(wrk) == []
 
 
 def test_cli_dead_rank_does_not_hang_rank_0(tmp_path):
