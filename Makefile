@@ -91,8 +91,8 @@ $(LIBDIR)/libmecat_hip_ixstats.so: $(HIP_SRCS) $(HIP_HDRS)
 wfprof: $(LIBDIR)/libmecat_hip_wfprof.so
 $(LIBDIR)/libmecat_hip_wfprof.so: $(HIP_SRCS) $(HIP_HDRS)
 	@mkdir -p build/wfprof $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -DWF_PROF -x hip -c $(CSRC)/seed.hip -o build/wfprof/seed.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC build/wfprof/seed.o $(filter-out build/seed.o,$(HIP_OBJS)) -o $@
+	$(HIPCC) $(HIPFLAGS) -DWF_PROF -x hip -c $(CSRC)/seed_chain.hip -o build/wfprof/seed_chain.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC build/wfprof/seed_chain.o $(filter-out build/seed_chain.o,$(HIP_OBJS)) -o $@
 
 ixknock: $(LIBDIR)/libmecat_hip_ixknock.so
 $(LIBDIR)/libmecat_hip_ixknock.so: $(HIP_SRCS) $(HIP_HDRS)

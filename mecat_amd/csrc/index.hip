@@ -254,7 +254,7 @@ __global__ __launch_bounds__(IDX_BLOCK) void idx_sort(const uint32_t* __restrict
 #include <chrono>
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// slot of a k-mer position in the seeding stage's relevance table: (position / ZV) mod 2^15, ZV = 2000 (seed.hip)
+// slot of a k-mer position in the seeding stage's relevance table: (position / ZV) mod 2^15, ZV = 2000 (seed_filter in seed_chain.hip, seed_strand.hip)
 __global__ __launch_bounds__(256) void idx_slots(const int32_t* __restrict__ offsets, int64_t n, uint16_t* __restrict__ slots) {
     const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i0 + 3 < n) {
@@ -270,7 +270,7 @@ __global__ __launch_bounds__(256) void idx_slots(const int32_t* __restrict__ off
 
 // The relevance filter of the seeding stage only needs each position's 2 kb-segment slot (15 bits): a second array at half the
 // bytes halves the sectors its bucket walk touches.
-// ---- bucket records with prefix counts at seven position cuts (seed.hip: the probe of a diagonal grid cell).
+// ---- bucket records with prefix counts at seven position cuts (the probe of a diagonal grid cell: seed_probe in seed_chain.hip, seed_strand.hip).
 // A query read of the reference volume itself only needs the bucket entries in front of its own copy (+ a few segments):
 // everything behind belongs to reads with higher ids, whose candidates get_candidates drops (pw_impl.cpp:370).  Bucket entries are
 // ascending positions, so "in front of position P" is a prefix of every bucket, and its length for seven fixed cuts P fits the

@@ -1,5 +1,5 @@
 // gather_peak.hip — how fast can an MI355X fetch short runs at random addresses?  The ceiling of the bucket walks of
-// seed_filter / seed_emit (mecat_amd/csrc/seed.hip): a 13-mer bucket is ~22 ascending entries somewhere in a multi-GB array,
+// seed_filter / seed_emit (mecat_amd/csrc/seed_chain.hip): a 13-mer bucket is ~22 ascending entries somewhere in a multi-GB array,
 // read by 16 lanes, 2 bytes (filter: table slots) or 4 bytes (emit: positions) per entry.
 //
 //   gather_peak [array_MB] [iters]      prints one JSON line: G runs/s and GB/s of useful bytes per variant

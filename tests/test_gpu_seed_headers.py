@@ -2,6 +2,7 @@
 persistent: one workgroup per CU, strands taken from a cursor, the next strand's headers requested while the current one is built.
 Every case: candidate lists == the oracle's == a second run with MECAT_SEED_FUSED_PROBE=0 (seed_probe first, seed_strand copies its
 headers from the km_* arrays), and the lookup / bucket-hit counters of both runs are equal."""
+import json
 import os
 from contextlib import contextmanager
 
@@ -12,7 +13,7 @@ import helpers as H
 
 pytestmark = pytest.mark.gpu
 
-SEGCAP = 6144          # FS_SEGCAP (seed.hip): k-mers of a strand whose headers fit the LDS of seed_strand
+SEGCAP = 6144          # FS_SEGCAP (seed_strand.hip): k-mers of a strand whose headers fit the LDS of seed_strand
 
 
 @pytest.fixture(scope="module")
@@ -247,3 +248,64 @@ def test_several_launches(hip, ctx):
     assert st["lookups"] == 2 * sum(kmers(L) for L in lens) and int(cnt.sum()) > 1000
     gi.free()
     v.free()
+
+
+def sort_passes(num_bases):
+    """seed_batch's rule: the segment ids of the reference volume (num_bases / 2000 is the highest) in passes of up to 11 bits"""
+    nbits = max(1, int(num_bases // 2000).bit_length())
+    return (nbits + 10) // 11
+
+
+def test_kernels_launched_per_path(hip, ctx):
+    """Which seeding kernels one seed_reads call launches, and how often, for every way through seed_batch, on the golden sets tiny
+    (PacBio gate 2 * min_kmer_match >= 6: relevance filter and strand pipeline on) and tiny_ont (nanopore gate in [4, 6): the wide filter,
+    no strand pipeline).  One batch each (the sets are far below the batch budget): seed_cand runs once.
+      pipeline on, every strand taken          seed_strand, seed_cand; no seed_probe, nothing of the chain
+      pipeline on, strands left (ROOM=64)      seed_strand, then seed_probe once and the chain behind it
+      MECAT_SEED_FUSED=0 / MECAT_SEED_FILTER=0 no seed_strand: seed_probe first, the chain with seed_filter (FILTER=0 turns the pipeline off too)
+      nanopore                                 the same with seed_filter_wide in the place of seed_filter
+    The chain = filter, seed_scan, seed_emit, one seed_sort_pass per 11 bits of a segment id, seed_build."""
+    G = json.load(open(os.path.join(H.GOLDEN, "golden.json")))
+
+    def load(name):
+        g = G["sets"][name]["gen"]
+        codes, lens = H.synth_reads(g["nreads"], g["L"], g["err"], g["genome"], g["seed"], g["ont"])
+        v = Vol(hip, ctx, codes, lens)
+        return v, hip.Index(ctx, v.gv), hip.default_params(g["ont"])
+
+    def chain(filter_kernel, passes):
+        return {"seed_probe": 1, filter_kernel: 1, "seed_scan": 1, "seed_emit": 1, "seed_sort_pass": passes, "seed_build": 1, "seed_cand": 1}
+
+    def launched(v, gi, p, **knobs):
+        with env(**knobs):
+            _, cnt, st = run(hip, ctx, gi, v, v, p)
+        assert int(cnt.sum()) > 100, knobs       # every path has hits to emit, sort and build
+        print(knobs, st)
+        return {k: n for k, n in st["kernels"].items() if k.startswith("seed_")}, st
+
+    v, gi, p = load("tiny")
+    passes = sort_passes(v.nb)
+    assert 2 * p.min_kmer_match >= 6 and passes == 1
+    got, st = launched(v, gi, p)
+    assert st["left"] == 0 and st["took"] > 0
+    assert got == {"seed_strand": 1, "seed_cand": 1}
+    got, st = launched(v, gi, p, MECAT_SEED_FUSED=0)
+    assert got == chain("seed_filter", passes) and (st["took"], st["left"]) == (0, 0)
+    got, st = launched(v, gi, p, MECAT_SEED_FILTER=0)
+    assert got == chain("seed_filter", passes) and (st["took"], st["left"]) == (0, 0)
+    got, st = launched(v, gi, p, MECAT_SEED_FUSED_ROOM=64)
+    assert st["left"] > 0                        # (a forward strand meets its own copy: hundreds of kept hits, 64 places)
+    assert got == dict(chain("seed_filter", passes), seed_strand=1)
+    gi.free()
+    v.free()
+
+    v, gi, p = load("tiny_ont")
+    passes = sort_passes(v.nb)
+    assert 4 <= 2 * p.min_kmer_match < 6 and passes == 1
+    got, st = launched(v, gi, p)
+    assert got == chain("seed_filter_wide", passes) and (st["took"], st["left"]) == (0, 0)
+    assert got["seed_sort_pass"] == sort_passes(v.nb)
+    gi.free()
+    v.free()
+    # (two passes: 2^11 segments and more, a volume of 4.1 Mbase — test_gpu_fullsize.py runs those)
+    assert [sort_passes(n) for n in (2000 * 2047 + 1999, 2000 * 2048, 2000 * (1 << 21))] == [1, 2, 2]
