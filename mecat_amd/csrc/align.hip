@@ -433,6 +433,8 @@ __global__ __launch_bounds__(AL_BLOCK) void dw_extend(const uint32_t* __restrict
 #define RCAP 1024
 #endif
 #define SEQ_WORDS2 48          // 736 bases + one 16-base window, 16 bases per word, no pad word
+// band_tol and max_d of a full block (SEG_BLK x SEG_BLK: every block but a unit's last), as the block set-up's f64 expressions give them
+constexpr int FULL_BAND_TOL = (int)(0.3 * SEG_BLK), FULL_MAX_D = (int)(.3 * (SEG_BLK + SEG_BLK));
 // Per-half LDS, 2.4 KB incl. the ring below (19 KB per workgroup of four waves: eight workgroups per CU).  There is no V[] array: row d
 // reads the furthest x of diagonals k - 1 and k + 1 of row d - 1 straight from that row's entries in the ring, at pbase + tt and
 // pbase + tt + 1 (inside the band they are entries of that row; at its two edges the entry between rows or a dropped diagonal: see
@@ -549,7 +551,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
     int qblk = 0, tblk = 0, last_block = 0, band_tol = 0, max_d = 0;
     // band = nslot diagonals from min_k; d = rows done.  The three values every lane adds its own 2 * sl to on every row are kept with
     // it added (`_l`: per lane): the row code then uses them as they are, and the band update moves all lanes by the same amount.
-    int best_m = -1, mk_l = 0, nslot = 0, aligned = 0, end_x = 0, end_k = 0, end_d = 0, end_mk = 0, end_ns = 0, d = 0;
+    int best_m = -1, mk_l = 0, nslot = 0, aligned = 0, end_x = 0, end_k = 0, end_d = 0, end_mk = 0, d = 0;
     int sepv = -1;              // what idle lanes store behind the row: ~(slots of the row | left cut of the row before << 8), see row_passes
     int cut = 0;                // diagonals the last band update dropped on the left (`first`)
     unsigned int lin_l = 0;     // ring position behind the last row (bytes, like the next two) + 2 sl
@@ -602,8 +604,10 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                     const int ext = min(qleft, tleft);
                     if (ext > SEG_BLK + 100) { qblk = SEG_BLK; last_block = 0; } else { qblk = max(ext, 0); last_block = 1; }
                     tblk = qblk;
-                    band_tol = (int)(0.3 * qblk);
-                    max_d = (int)(2.0 * ca.error_rate * (qblk + qblk));
+                    if (last_block) {
+                        band_tol = (int)(0.3 * qblk);
+                        max_d = (int)(2.0 * ca.error_rate * (qblk + qblk));
+                    } else { band_tol = FULL_BAND_TOL; max_d = ca.full_max_d; }      // (of the launch: cns_forward_launch)
                     blk_log0 = logpos;
                     if (logend - logpos < (unsigned)max_d) { cns_bad = true; max_d = 0; }      // the rows of this block may not fit the unit's share of the log
                 } else {
@@ -611,15 +615,26 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                     qblk = min(qleft, (int)(tleft + tleft * 0.2));
                     tblk = min(tleft, (int)(qleft + qleft * 0.2));
                     last_block = 1;
-                } else { qblk = SEG_BLK; tblk = SEG_BLK; last_block = 0; }
-                qblk = max(qblk, 0);
-                tblk = max(tblk, 0);
-                band_tol = (int)(0.3 * (qblk > tblk ? qblk : tblk));
-                max_d = (int)(.3 * (qblk + tblk));
+                    qblk = max(qblk, 0);
+                    tblk = max(tblk, 0);
+                    band_tol = (int)(0.3 * (qblk > tblk ? qblk : tblk));
+                    max_d = (int)(.3 * (qblk + tblk));
+                } else { qblk = SEG_BLK; tblk = SEG_BLK; last_block = 0; band_tol = FULL_BAND_TOL; max_d = FULL_MAX_D; }      // no f64 for a full block
                 }
-                for (int w = sl; w < SEQ_WORDS2; w += 32) {      // word w = logical bases 16w .. 16w+15, first base in the low bits
-                    S.Qp[w] = (w * 16 < qblk + 32) ? view_word_le(q, qidx + w * 16) : 0u;
-                    S.Tp[w] = (w * 16 < tblk + 32) ? view_word_le(t, tidx + w * 16) : 0u;
+                // Staging: word w = logical bases 16w .. 16w+15, first base in the low bits.  Only the words that hold a base of the
+                // block are written (16 w < blk); the others keep what an earlier block left there, and no result depends on it:
+                // a live diagonal has x <= q_len and its window is words x >> 4 and (x >> 4) + 1, so every base it sees at or beyond
+                // q_len (t_len for the target) sits at window offset >= lim = min(q_len - x, t_len - y).  A first difference in
+                // front of lim lies inside the valid bases of both sequences, and anything at or behind lim is clamped away by
+                // v_min3_i32(m, lim, 16); the end test lim == nn is decided by the same two cases.  Idle lanes keep nothing.
+                // Words 32 .. are staged only when a half in set-up has a block of more than 512 bases (a last block; the test is
+                // wave-uniform): a full block stages in one trip.
+                static_assert((SEG_BLK + 99) * 6 / 5 <= 16 * (SEQ_WORDS2 - 1), "the longest block and one 16-base window fit the staged words");
+                const int trips = BALLOT(max(qblk, tblk) > 512) ? 2 : 1;
+#pragma unroll 1
+                for (int w = sl, i = 0; i < trips; w += 32, ++i) {      // (blk <= 1.2 * (SEG_BLK + 99): 16 w < blk keeps w below SEQ_WORDS2)
+                    if (w * 16 < qblk) S.Qp[w] = view_word_le(q, qidx + w * 16);
+                    if (w * 16 < tblk) S.Tp[w] = view_word_le(t, tidx + w * 16);
                 }
                 // The reference zero-fills V per block (:232-233); row d only reads diagonals written by row d - 1, except row 0,
                 // which reads V[k_offset - 1] and V[k_offset + 1]: the two zeros in front of row 0.
@@ -965,7 +980,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
             hkey = half_min(hkey);
             if (inblock && hkey != 0x7fffffff) {
                 aligned = 1; end_k = (hkey >> 10) - k_offset; end_x = hkey & 1023; end_d = d;
-                end_mk = emk_l - 2 * sl; end_ns = en;
+                end_mk = emk_l - 2 * sl;
                 dlim = 0;
             }
             d += 1;
@@ -984,50 +999,54 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
         const int end_y = end_x - end_k;
         const int aln_size = (end_x + end_y + end_d) / 2;
         int cd = end_d, ck = end_k, cx2 = end_x;
-        int qcnt = 0, tcnt = 0, acnt = 0, found = 0;
+        int acnt = 0, found = 0;
         bool tracing = CNS ? (has_aln && !last_block) : has_aln;      // (CNS: a last block keeps all of its columns, dw.cpp:353-358)
-        // Rows are walked back over the entries between them: behind row r sits ~(slots of r | left cut of row r - 1 << 8).  clin / cmin /
-        // cns: ring position, first diagonal and slots of row cd (the row that reached the end is the row that ran last).
+        // Rows are walked back over the entries between them: behind row r sits ~(slots of r | left cut of row r - 1 << 8).  clin / cmin:
+        // ring position and first diagonal of row cd (the row that reached the end is the row that ran last); sepc: the entry behind row
+        // cd — what a step reads in front of row cd (the entry behind row cd - 1) is that entry of the next step, so only the first one
+        // is read here (the band update behind the end row has replaced the live copy of it).
         const unsigned int lin_u = lin_l - 2u * sl;
         unsigned int clin = rlin_l - 2u * sl;
-        int cmin = end_mk, cns = end_ns;
+        int cmin = end_mk;
+        int sepc = ~ring_ld(rbase, lin_u - 2u);
         while (BALLOT(tracing)) {
             if (tracing) {
-                int x1 = 0, pre_k = 0, takes_q = 0;
-                if (cd > 0) {
-                    const int sc = ~ring_ld(rbase, clin + 2u * (unsigned)cns), sp = ~ring_ld(rbase, clin - 2u);
-                    const int pcut = (sc >> 8) & 127, pns = sp & 255;
-                    const unsigned int plin = clin - 2u - 2u * (unsigned)pns;
-                    // (128: what the idle lanes of the last row's passes may have written behind it, see row_passes; a cut of 127 or
-                    // more is not recorded)
-                    if (pcut == 127 || lin_u - plin > 2 * RCAP - 128) { handover = true; tracing = false; }
-                    else {
-                        const int pmin = cmin - 2 * pcut + 1, pmax = pmin + 2 * (pns - 1), cmax = cmin + 2 * (cns - 1);
-                        const int kl = ck - 1, kr = ck + 1;
-                        int vl = 0, vr = 0;
-                        if (kl >= pmin && kl <= pmax) vl = ring_ld(rbase, plin + (unsigned)(kl - pmin));      // entry (kl - pmin) / 2, two bytes each
-                        if (kr >= pmin && kr <= pmax) vr = ring_ld(rbase, plin + (unsigned)(kr - pmin));
-                        if (ck == cmin || (ck != cmax && vl < vr)) { x1 = vr; pre_k = kr; takes_q = 0; }
-                        else { x1 = vl + 1; pre_k = kl; takes_q = 1; }
-                        clin = plin; cmin = pmin; cns = pns;
-                    }
-                }
-                if (tracing) {
-                    const int sn = cx2 - x1;
-                    if (sn >= 4) { acnt += 4; qcnt += 4; tcnt += 4; found = 1; tracing = false; }
-                    else {
-                        acnt += sn; qcnt += sn; tcnt += sn;
-                        if (cd == 0) tracing = false;
-                        else {
-                            acnt += 1;
-                            if (takes_q) { qcnt += 1; cx2 = x1 - 1; } else { tcnt += 1; cx2 = x1; }
-                            ck = pre_k;
-                            --cd;
-                        }
-                    }
-                }
+                // The path came to (cx2, diagonal ck) of row cd from diagonal ck - 1 (vl, one query base) or ck + 1 (vr, one target base)
+                // of row cd - 1 and then ran along the snake from x1: x1 = max(vl + 1, vr), from the right when vl < vr, and the point it
+                // left row cd - 1 at is x = max(vl, vr).  A neighbour outside row cd - 1 counts as -1, which is all the reference's edge
+                // tests (k == min_k: from the right; k == max_k: from the left) do: inside row cd - 1 but outside the band that row cd
+                // was cut to, the left neighbour of min_k has vl + 1 < vr and the right neighbour of max_k vr < vl + 1 (see row_passes).
+                // One straight line of selects (nested conditions cost a copy of every carried value per branch); in row 0 (cd == 0:
+                // the snake runs back to x = 0) the ring reads are made and not used — a ring address is always inside the ring.
+                const bool up = cd > 0;
+                const int sp = ~ring_ld(rbase, clin - 2u);
+                const int pcut = (sepc >> 8) & 127, pns = sp & 255;
+                const unsigned int plin = clin - 2u - 2u * (unsigned)pns;
+                // the row in front has left the ring (128: what the idle lanes of the last row's passes may have written behind it, see
+                // row_passes), or its cut was 127 or more and is not recorded: the unit is handed over, whatever else this step computes
+                const bool lost = up && (pcut == 127 || lin_u - plin > 2 * RCAP - 128);
+                const int pmin = cmin - 2 * pcut + 1;
+                // byte offsets of the two neighbours in row cd - 1 (two bytes per diagonal, diagonals two apart): one unsigned compare
+                // each against the row's last offset
+                const unsigned int ol = (unsigned)(ck - 1 - pmin), olast = 2u * (unsigned)pns - 2u;
+                const int rl = ring_ld(rbase, plin + ol), rr = ring_ld(rbase, plin + ol + 2u);
+                const int vl = ol <= olast ? rl : -1, vr = ol + 2u <= olast ? rr : -1;
+                const int x1 = up ? max(vl + 1, vr) : 0;
+                const int sn = cx2 - x1;
+                const bool run4 = sn >= 4;                       // the run of four matches: the walk ends in front of it
+                const bool go = up && !run4 && !lost;            // otherwise one more row back (in row 0 there is none: no run found)
+                acnt += run4 ? 4 : sn + (up ? 1 : 0);
+                cx2 = run4 ? cx2 - 4 : (up ? max(vl, vr) : 0);
+                ck = go ? ck + (vl < vr ? 1 : -1) : ck;
+                cd -= go ? 1 : 0;
+                found = run4 ? 1 : 0;
+                clin = plin; cmin = pmin; sepc = sp;
+                handover = handover || lost;
+                tracing = go;
             }
         }
+        // query / target bases the walk took off the end of the alignment: it stands at (cx2, diagonal ck)
+        int qcnt = end_x - cx2, tcnt = end_y - (cx2 - ck);
         const int trim_ok = has_aln && found && (aln_size - acnt >= 2);
         DWS_T(t_e);
         DWS_ADD(tk_trace, t_d, t_e);
@@ -1213,9 +1232,11 @@ int cns_forward_launch(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* r
     HIPCHK(hipMemsetAsync(d_cur, 0, 16, c->stream));
     const int waves = getenv("MECAT_CNS_WAVES") ? std::max(4, std::min(32, atoi(getenv("MECAT_CNS_WAVES")))) : 4 * CNS_FWD_WAVES_PER_SIMD;
     const int grid = std::min(c->num_cus * waves / AL_WAVES, (n + AL_WAVES - 1) / AL_WAVES);
+    CnsFwdArgs a = args;
+    a.full_max_d = (int)(2.0 * a.error_rate * (SEG_BLK + SEG_BLK));      // the block set-up's expression at qblk = SEG_BLK
     LAUNCH(c, "cns_forward", dw_extend2<true>, grid, AL_BLOCK, 0, (const uint32_t*)ref->d_pac, (const mhip_offset_t*)ref->d_offs,
            (const uint32_t*)reads->d_pac, (const mhip_offset_t*)reads->d_offs, (const mhip_aln_job*)d_jobs, n, (DirResult*)nullptr,
-           (DwHandover*)nullptr, (unsigned int*)nullptr, d_cur, (unsigned long long*)c->d_counters, args);
+           (DwHandover*)nullptr, (unsigned int*)nullptr, d_cur, (unsigned long long*)c->d_counters, a);
     return 0;
 }
 

@@ -43,6 +43,7 @@ struct CnsFwdArgs {
     unsigned int* hand_units;      // units for cns_extend: [0] their number, then the units
     CnsDir* dres;                  // [units]
     int dir_cols_cap;
+    int full_max_d;                // max_d of a full block, int(2 error_rate (SEG_BLK + SEG_BLK)): filled in by cns_forward_launch
     int* err_flag;                 // a direction needed more than dir_cols_cap columns
 };
 
