@@ -1,6 +1,7 @@
 # Top-level build.  `make all` = everything that can be built on this machine.
 #   hip     mecat_amd/lib/libmecat_hip.so   HIP kernels + C-ABI (gfx950)
 #           mecat_amd/lib/libcns_poa_host.so   the POA window routine (csrc/cns_poa.h) compiled for the host, no HIP: the tests' expected values
+#                                              and the corrected reads' record rule (csrc/cns_reads.h), the function the record kernel runs
 #   host    mecat_amd/bin/mecat2pw          C++ host driver (drop-in CLI) on top of the C-ABI
 #   synth   mecat_amd/lib/libsynth.so + mecat_amd/bin/synth_reads   synthetic read generator
 #   oracle  oracle/liboracle.so             CPU restatement (test infrastructure)
@@ -23,7 +24,7 @@ all: synth oracle hip host
 	@if [ -d /root/reference/src ]; then $(MAKE) ref; fi
 
 hip: $(LIBDIR)/libmecat_hip.so $(LIBDIR)/libcns_poa_host.so
-$(LIBDIR)/libcns_poa_host.so: $(CSRC)/cns_poa_host.cpp $(CSRC)/cns_poa.h
+$(LIBDIR)/libcns_poa_host.so: $(CSRC)/cns_poa_host.cpp $(CSRC)/cns_poa.h $(CSRC)/cns_reads.h
 	@mkdir -p $(LIBDIR)
 	$(CXX) -O2 -std=c++17 -fPIC -shared -Wall -I$(CSRC) $< -o $@
 build/%.o: $(CSRC)/%.hip $(HIP_HDRS)

@@ -414,8 +414,8 @@ int  mhip_debug_cns_table(mhip_ctx* ctx, const char* buf, int64_t bytes, const i
  * the table is built on the device whether or not MHIP_CNS_WANT_TABLE is set, but it is copied to the host only with that bit; with
  * MHIP_CNS_WANT_PLAN alone neither strings nor tables cross the PCIe link.  Without MHIP_CNS_WANT_PLAN the six plan outputs come back
  * NULL / 0 (their pointers may be NULL then) and min_cov / min_size are not looked at.  All buffers are released with mhip_cns_free.
- * Retrieving the windows' substrings: mhip_cns_accept_templates_pieces below.  The POA and the output of the corrected reads stay with
- * the caller. */
+ * Retrieving the windows' substrings: mhip_cns_accept_templates_pieces below; the POA: mhip_cns_accept_templates_poa; the corrected
+ * reads: mhip_cns_accept_templates_reads. */
 typedef struct { int32_t template_index, beg, end, n_anchors; int64_t win_begin, win_end; } mhip_cns_segment;
 typedef struct { int32_t sb, se, cov, segment; } mhip_cns_window;       /* segment: index into out_segments */
 #define MHIP_CNS_WANT_PLAN 4
@@ -492,7 +492,7 @@ int  mhip_debug_cns_pieces(mhip_ctx* ctx, const char* buf, int64_t bytes, const 
  * with MHIP_CNS_WANT_PIECES: PLAN | POA alone moves no strings, tables or pieces over the PCIe link.  Without the bit the call is
  * mhip_cns_accept_templates_pieces (the two outputs come back NULL, their pointers may be NULL).  _pieces, _plan and _ex keep refusing
  * the bit.  The output is the same bytes on every run; release with mhip_cns_free.  Putting the segments together from the windows'
- * strings (meap_consensus_one_segment's target) and the output of the corrected reads stay with the caller. */
+ * strings (meap_consensus_one_segment's target) and the corrected reads: mhip_cns_accept_templates_reads below. */
 #define MHIP_CNS_WANT_POA 16
 int  mhip_cns_accept_templates_poa(mhip_ctx* ctx, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin,
                                    int num_templates, int tech, int min_align_size, double min_mapping_ratio, int num_threads, int want,
@@ -514,6 +514,71 @@ int  mhip_debug_cns_poa(mhip_ctx* ctx, const char* buf, int64_t bytes, const int
                         const int32_t* send, int n_pairs, const int32_t* windows, int n_windows, char** out_cns, int64_t** out_cns_begin);
 /* test hook: the last POA launch of the process: out[0] = windows that went to cns_poa_large, out[1] = launches of it (chunks) */
 void mhip_debug_cns_poa_last(int64_t* out /* [2] */);
+/* ---- the corrected reads (cns_reads.hip): the rest of consensus_worker (mecat_correction.cpp:203-239), behind a slice's POA while its
+ * table, plan and consensus strings are still in device memory.
+ *   a segment's target   meap_consensus_one_segment, :88-107: positions of the segment [beg, end) in front of its first FMAT position give
+ *                        nothing; from there every FMAT position i, ascending, gives table[i].base and, when the window with sb == i is
+ *                        listed and its consensus has more than two letters, that string without its first and last letter.  The length
+ *                        is n_anchors + the sum over the segment's windows of max(0, len - 2): lengths, the size filter and every output
+ *                        position come from prefix sums before a letter is written.
+ *   records              :233 and output_cns_result, :155-188: a target shorter than min_size gives nothing; one of at most 60 000 letters
+ *                        gives one record with range (beg, end); a longer one is cut into blocks of 49 000 letters overlapping by 10 000,
+ *                        the first block whose end reaches size - 11 000 ending at `size` (csrc/cns_reads.h: one function for the kernel
+ *                        and for libcns_poa_host.so).  A block [L, R) has range_beg = L + beg and range_end = R + beg where R < size and
+ *                        R + beg < end, otherwise end.  A target is stored once: the records of a cut segment point into overlapping
+ *                        stretches of it, record r owning out_seq[seq_begin .. seq_begin + size).
+ * read_id is the sid of the template's candidate records (what the reference passes as read_id), `segment` the batch-wide segment number
+ * (the index into out_segments when those are copied).  Template t owns out_reads[out_read_begin[t] .. out_read_begin[t + 1]), in
+ * segment order, then block order: the order in which consensus_worker pushes them for that template.
+ * mhip_cns_accept_templates_reads is mhip_cns_accept_templates_poa with MHIP_CNS_WANT_READS allowed in `want`, alone or with any other
+ * bit.  With the bit set the table, plan, pieces and POA are computed on the device whether or not their own bits are set, and each is
+ * copied to the host only with its own bit: MHIP_CNS_WANT_READS alone moves the accepted records and the reads over the PCIe link, nothing
+ * else (the outputs of the other bits come back NULL / 0).  min_cov and min_size are looked at (min_size >= 2, min_cov >= 1).
+ * MHIP_CNS_WANT_PIECES and MHIP_CNS_WANT_POA keep needing MHIP_CNS_WANT_PLAN.  Without the bit the call is mhip_cns_accept_templates_poa,
+ * byte for byte (the four outputs come back NULL / 0, their pointers may be NULL); _poa, _pieces, _plan and _ex keep refusing the bit.
+ * The host waits once more per slice, for the two totals (letters, records) that size the output.  A flag word set by the kernels —
+ * an index from the data left its array, or the letters written are not the letters counted — makes the call fail; nothing is
+ * truncated.  The output is the same bytes on every run; out_read_begin has num_templates + 1 entries; release with mhip_cns_free. */
+typedef struct { int32_t read_id, range_beg, range_end, size; int64_t seq_begin; int32_t template_index, segment; } mhip_cns_read;
+#define MHIP_CNS_WANT_READS 32
+int  mhip_cns_accept_templates_reads(mhip_ctx* ctx, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin,
+                                     int num_templates, int tech, int min_align_size, double min_mapping_ratio, int num_threads, int want,
+                                     int min_cov, int min_size, mhip_cns_accepted** out_accepted, int64_t* out_count, char** out_strings,
+                                     int64_t* out_strings_bytes, int64_t* out_jobs, mhip_cns_table_item** out_table, uint8_t** out_ident,
+                                     int64_t** out_table_begin /* [num_templates + 1] */, mhip_cns_segment** out_segments,
+                                     int64_t** out_seg_begin /* [num_templates + 1] */, mhip_cns_window** out_windows, int64_t* out_n_windows,
+                                     int32_t** out_eranges, int64_t** out_erange_begin /* [num_templates + 1] */,
+                                     mhip_cns_piece** out_pieces, int64_t** out_piece_begin /* [*out_n_windows + 1] */,
+                                     char** out_cns, int64_t** out_cns_begin /* [*out_n_windows + 1] */,
+                                     mhip_cns_read** out_reads, int64_t** out_read_begin /* [num_templates + 1] */, char** out_seq,
+                                     int64_t* out_seq_bytes);
+/* The reference's text for n records (reads_correction_can.cpp:44-46): ">" read_id "_" range_beg "_" range_end "_" size, newline, the
+ * letters, newline.  Host C++ only.  The two gates in front of the reference's loop (:32-33) need no code here: a template with fewer
+ * than min_cov candidates cannot reach coverage min_cov anywhere, and a read shorter than 0.95 * min_size cannot hold a run of that
+ * length, so neither can have a segment.  Refused: a record that leaves seq[0 .. seq_bytes).  -> *out_text (malloc'ed, no terminator,
+ * release with mhip_cns_free), *out_bytes */
+int  mhip_cns_format_reads(const mhip_cns_read* reads, int64_t n, const char* seq, int64_t seq_bytes, char** out_text, int64_t* out_bytes);
+/* test hook: the read kernels alone on host-supplied arrays: tables and ident bytes of n_tmpl templates (template k at [table_begin[k],
+ * table_begin[k + 1]), table_begin[0] == 0) with read ids read_id[k], n_seg segment records and n_win window records as the plan gives
+ * them (numbers counted from 0, n_anchors as given), the windows' strings cns[cns_begin[w] .. cns_begin[w + 1]).  Refused before
+ * anything is launched: min_size < 2; segments that are not in template order, a segment outside its template or not beg < end; segments
+ * whose window ranges are not win_begin <= win_end, ascending and inside [0, n_win]; windows that are not sb < se, not ascending or not
+ * disjoint inside their segment, that lie outside their segment or name another one; a cns_begin that does not start at 0 or does not
+ * ascend.  What only the kernels can see (a window that does not start on an FMAT position, an n_anchors that is not the segment's) sets
+ * the flag word: the call fails.  Outputs as mhip_cns_accept_templates_reads' four. */
+int  mhip_debug_cns_reads(mhip_ctx* ctx, const mhip_cns_table_item* table, const uint8_t* ident, const int64_t* table_begin, int n_tmpl,
+                          const int32_t* read_id, const mhip_cns_segment* segments, int64_t n_seg, const mhip_cns_window* windows,
+                          int64_t n_win, const char* cns, const int64_t* cns_begin, int min_size, mhip_cns_read** out_reads,
+                          int64_t** out_read_begin /* [n_tmpl + 1] */, char** out_seq, int64_t* out_seq_bytes);
+/* test hook: the whole back end on ONE template through the launchers the accept stage uses — table, plan, pieces, POA, reads: the
+ * alignments in mhip_debug_cns_pieces' layout, the template's letters (tmpl_len of them), tech (0: get_effective_ranges over the
+ * alignments' (soff, send); 1: the whole read), min_cov, min_size and the read id.  Refused before anything is launched: what
+ * mhip_debug_cns_table and mhip_debug_cns_pieces refuse (a mismatch column, a pair that leaves the template; more than 100 pairs,
+ * len < 1, a pair outside the buffer, negative coordinates, send - soff != the bases of saln), min_size < 2, min_cov < 1.
+ * -> *out_reads [*out_n_reads], *out_seq [*out_seq_bytes] (release with mhip_cns_free) */
+int  mhip_debug_cns_correct(mhip_ctx* ctx, const char* buf, int64_t bytes, const int64_t* off, const int32_t* len, const int32_t* soff,
+                            const int32_t* send, int n_pairs, const char* tmpl_letters, int tmpl_len, int tech, int min_cov, int min_size,
+                            int read_id, mhip_cns_read** out_reads, int64_t* out_n_reads, char** out_seq, int64_t* out_seq_bytes);
 /* mhip_cns_free does not return a string buffer to the system at once: the library keeps the LARGEST released one (gigabytes — about
  * 14 GB for a config-2-sized batch) and hands it out again to the next batch that fits, because first-touching fresh pages costs
  * more than the batch's GPU time.  The parked buffer belongs to the process, not to a context (mhip_ctx_destroy leaves it).  This call

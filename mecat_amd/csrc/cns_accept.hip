@@ -23,6 +23,9 @@
 // mhip_cns_accept_templates_pieces adds what the reference does with a listed window first: every accepted alignment's part of it
 // (CnsAln::retrieve_aln_subseqs, reads_correction_aux.h:47-68, called by meap_cns_one_indel, :62-78), as descriptors, behind a slice's
 // plan while its strings are still in device memory — cns_pieces.hip.
+// mhip_cns_accept_templates_poa adds the POA consensus of every listed window (meap_cns_one_indel, :62-78) — cns_poa.hip — and
+// mhip_cns_accept_templates_reads what the reference ends with: every segment's target put together from the anchors' letters and the
+// windows' strings (:88-107), the size filter and output_cns_result's records (:233, :155-188), behind a slice's consensus — cns_reads.hip.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -39,6 +42,7 @@
 #include "cns_plan.h"
 #include "cns_poa_dev.h"
 #include "cns_ranges.h"
+#include "cns_reads.h"
 #include "cns_replay.h"
 #include "cns_slices.h"
 #include "cns_strings.h"
@@ -46,7 +50,7 @@
 
 namespace {
 
-const int WANT_STR = MHIP_CNS_WANT_STRINGS, WANT_TAB = MHIP_CNS_WANT_TABLE, WANT_PLAN = MHIP_CNS_WANT_PLAN, WANT_PIECES = MHIP_CNS_WANT_PIECES, WANT_POA = MHIP_CNS_WANT_POA;
+const int WANT_STR = MHIP_CNS_WANT_STRINGS, WANT_TAB = MHIP_CNS_WANT_TABLE, WANT_PLAN = MHIP_CNS_WANT_PLAN, WANT_PIECES = MHIP_CNS_WANT_PIECES, WANT_POA = MHIP_CNS_WANT_POA, WANT_READS = MHIP_CNS_WANT_READS;
 
 struct CmpByScore {      // CmpExtensionCandidateByScore, mecat_correction.cpp:362-370
     bool operator()(const mhip_ext_candidate& a, const mhip_ext_candidate& b) const {
@@ -64,6 +68,7 @@ struct AcceptCall {
     mhip_cns_table_item** table = nullptr; uint8_t** ident = nullptr; int64_t** table_begin = nullptr;
     mhip_cns_segment** segments = nullptr; int64_t** seg_begin = nullptr; mhip_cns_window** windows = nullptr; int64_t* n_windows = nullptr; int32_t** eranges = nullptr; int64_t** erange_begin = nullptr;
     mhip_cns_piece** pieces = nullptr; int64_t** piece_begin = nullptr; char** cns = nullptr; int64_t** cns_begin = nullptr;
+    mhip_cns_read** reads = nullptr; int64_t** read_begin = nullptr; char** seq = nullptr; int64_t* seq_bytes = nullptr;
 };
 
 template <typename T> void clear_out(T* p) { if (p) *p = T(); }
@@ -72,17 +77,20 @@ template <typename T> void clear_out(T* p) { if (p) *p = T(); }
 int validate(const AcceptCall& a, int allowed) {
     const int want = a.want;
     const char *plan = (allowed & WANT_PLAN) ? " | MHIP_CNS_WANT_PLAN" : "", *pieces = (allowed & WANT_PIECES) ? " | MHIP_CNS_WANT_PIECES" : "", *poa = (allowed & WANT_POA) ? " | MHIP_CNS_WANT_POA" : "";
-    if (want == 0 || (want & ~allowed)) { mhip_set_error("cns accept: want = %d (MHIP_CNS_WANT_STRINGS | MHIP_CNS_WANT_TABLE%s%s%s)", want, plan, pieces, poa); return -1; }
+    const char* reads = (allowed & WANT_READS) ? " | MHIP_CNS_WANT_READS" : "";
+    if (want == 0 || (want & ~allowed)) { mhip_set_error("cns accept: want = %d (MHIP_CNS_WANT_STRINGS | MHIP_CNS_WANT_TABLE%s%s%s%s)", want, plan, pieces, poa, reads); return -1; }
     if ((want & WANT_PIECES) && !(want & WANT_PLAN)) { mhip_set_error("cns accept: want = %d: MHIP_CNS_WANT_PIECES needs MHIP_CNS_WANT_PLAN (pieces belong to the plan's windows)", want); return -1; }
     if ((want & WANT_POA) && !(want & WANT_PLAN)) { mhip_set_error("cns accept: want = %d: MHIP_CNS_WANT_POA needs MHIP_CNS_WANT_PLAN (the consensus belongs to the plan's windows)", want); return -1; }
     if ((want & WANT_POA) && (!a.cns || !a.cns_begin)) { mhip_set_error("cns accept: the consensus was asked for without a place to put it"); return -1; }
     if ((want & WANT_PIECES) && (!a.pieces || !a.piece_begin)) { mhip_set_error("cns accept: the pieces were asked for without a place to put them"); return -1; }
     if ((want & WANT_TAB) && (!a.table || !a.ident || !a.table_begin)) { mhip_set_error("cns accept: the table was asked for without a place to put it"); return -1; }
     if ((want & WANT_PLAN) && (!a.segments || !a.seg_begin || !a.windows || !a.n_windows || !a.eranges || !a.erange_begin)) { mhip_set_error("cns accept: the plan was asked for without a place to put it"); return -1; }
-    if ((want & WANT_PLAN) && (a.min_size < 2 || a.min_cov < 1)) { mhip_set_error("cns accept: the plan needs min_size >= 2 and min_cov >= 1 (%d, %d)", a.min_size, a.min_cov); return -1; }
+    if ((want & WANT_READS) && (!a.reads || !a.read_begin || !a.seq || !a.seq_bytes)) { mhip_set_error("cns accept: the reads were asked for without a place to put them"); return -1; }
+    if ((want & (WANT_PLAN | WANT_READS)) && (a.min_size < 2 || a.min_cov < 1)) { mhip_set_error("cns accept: the plan needs min_size >= 2 and min_cov >= 1 (%d, %d)", a.min_size, a.min_cov); return -1; }
     clear_out(a.accepted); clear_out(a.count); clear_out(a.strings); clear_out(a.strings_bytes); clear_out(a.jobs); clear_out(a.table); clear_out(a.ident); clear_out(a.table_begin);
     clear_out(a.segments); clear_out(a.seg_begin); clear_out(a.windows); clear_out(a.n_windows); clear_out(a.eranges); clear_out(a.erange_begin);
     clear_out(a.pieces); clear_out(a.piece_begin); clear_out(a.cns); clear_out(a.cns_begin);
+    clear_out(a.reads); clear_out(a.read_begin); clear_out(a.seq); clear_out(a.seq_bytes);
     return 0;
 }
 
@@ -102,14 +110,18 @@ struct Slice {
 // A slice's part of the plan, in host buffers of its own (the sizes are known slice by slice only), put together at the hand-over; the
 // records are final when they leave the device.  win.bad is CnsPlanDev::d_bad: copied with the windows and looked at in the hand-over
 // only, after every slice has run (an overflow of the segment slots is refused by cns_plan_launch at once).  pc: cns_pieces.hip's slots,
-// cn: cns_poa.hip's bytes, both with begin[] per window of the slice.
-struct PlanSlice { SliceOut seg, win, pc, cn; };
+// cn: cns_poa.hip's bytes, both with begin[] per window of the slice.  rd, sq: cns_reads.hip's records and letters (counts the host knows)
+// with tbegin[nt + 1], the first record of each of the slice's templates [t0, t0 + nt).
+struct PlanSlice { SliceOut seg, win, pc, cn, rd, sq; CnsBuf<int64_t> tbegin; int t0 = 0, nt = 0; };
 
 // the state of one call
 struct Batch {
     const AcceptCall& a;
     mhip_ctx* const c;
-    const bool want_str, want_tab, want_plan, want_pieces, want_poa, build_tab;      // build_tab: the plan reads the table: built on the device either way, copied only when asked for
+    const bool want_str, want_tab, want_plan, want_pieces, want_poa, want_reads;
+    // build_*: what the outputs asked for read is built on the device either way and copied only when asked for itself — the plan reads the
+    // table, the reads read table, plan and consensus
+    const bool build_plan, build_pieces, build_poa, build_tab;
     const int threads, start_id, min_run;
     const CnsReplayRules rules;
     const double error_rate;                   // mecat_correction.cpp:431 / :494
@@ -139,10 +151,13 @@ struct Batch {
     std::vector<int32_t> ER;
     int64_t seg_total = 0, win_total = 0;
     long long poa_large = 0, poa_chunks = 0;      // windows that went to cns_poa_large, and its launches
+    double reads_wait = 0;                        // host seconds in cns_reads_launch's waits (counted with the plan's as well)
+    int64_t reads_total = 0, seq_total = 0;
 
     explicit Batch(const AcceptCall& a_)
         : a(a_), c(a_.c), want_str(a_.want & WANT_STR), want_tab(a_.want & WANT_TAB), want_plan(a_.want & WANT_PLAN), want_pieces(a_.want & WANT_PIECES), want_poa(a_.want & WANT_POA),
-          build_tab(want_tab || want_plan), threads(std::max(1, a_.num_threads)), start_id(a_.vol->start_read_id), min_run(want_plan ? cns_plan_min_run(a_.min_size) : 0),
+          want_reads(a_.want & WANT_READS), build_plan(want_plan || want_reads), build_pieces(want_pieces || want_poa || want_reads), build_poa(want_poa || want_reads),
+          build_tab(want_tab || build_plan), threads(std::max(1, a_.num_threads)), start_id(a_.vol->start_read_id), min_run(build_plan ? cns_plan_min_run(a_.min_size) : 0),
           rules{200, a_.tech == 0 ? 60 : 100, a_.min_mapping_ratio - 0.02}, error_rate(a_.tech == 0 ? 0.15 : 0.20) {}
     // no copy may still be writing into a buffer that goes: the body runs before any member is released
     ~Batch() {
@@ -250,12 +265,12 @@ int align_slice(Batch& b, const Slice& sl, int set) {
 void replay_slice(const Batch& b, Slice& sl) {
     const AcceptCall& a = b.a;
     const int nt = sl.t1 - sl.t0;
-    sl.acc.assign((size_t)nt, std::vector<int32_t>()); sl.er.assign((size_t)(b.want_plan ? nt : 0), std::vector<int32_t>());
+    sl.acc.assign((size_t)nt, std::vector<int32_t>()); sl.er.assign((size_t)(b.build_plan ? nt : 0), std::vector<int32_t>());
     parallel_for(nt, b.threads, [&](int64_t tl) {
         const int64_t t = sl.t0 + tl;
         if (a.tmpl_begin[t + 1] == a.tmpl_begin[t]) return;
         sl.acc[(size_t)tl] = cns_replay_template(a.cands, a.tmpl_begin, b.res.data(), b.jfirst.data(), t, b.rules);
-        if (b.want_plan) {                                         // cns_vec.get_mapping_ranges + get_effective_ranges, :445-447 (tech 1: :509)
+        if (b.build_plan) {                                         // cns_vec.get_mapping_ranges + get_effective_ranges, :445-447 (tech 1: :509)
             std::vector<std::pair<int32_t, int32_t>> mr;
             for (const int32_t ji : sl.acc[(size_t)tl]) mr.emplace_back(b.res[(size_t)ji].soff, b.res[(size_t)ji].send);
             cns_effective_ranges(mr, b.read_size((int)t), a.tech, a.min_size, sl.er[(size_t)tl]);
@@ -284,7 +299,7 @@ struct SliceWork {
     int64_t na = 0, tw0 = 0, tw = 0;       // accepted alignments; the slice's table words in the batch's
     size_t a0 = 0;                         // its first accepted record in Avec
     char* d_str = nullptr; uint32_t* d_tab = nullptr; uint8_t* d_id = nullptr;
-    CnsPlanDev pd; CnsPiecesDev qd; CnsPoaDev od;
+    CnsPlanDev pd; CnsPiecesDev qd; CnsPoaDev od; CnsReadsDev rd;
     PlanSlice* ps = nullptr;               // with a plan launched
 };
 
@@ -388,9 +403,9 @@ int launch_plan(Batch& b, const Slice& sl, SliceWork& w) {
     PlanSlice& ps = b.plan.back();
     w.ps = &ps;
     ps.seg.count = pd.nseg; ps.win.count = pd.nwin; ps.pc.n = ps.cn.n = pd.nwin;               // (the windows own nothing until pieces and consensus have run)
-    const bool room = slice_out_alloc(ps.seg, sizeof(mhip_cns_segment), pd.nseg, -1, b.threads) && slice_out_alloc(ps.win, sizeof(mhip_cns_window), pd.nwin, -1, b.threads);
+    const bool room = !b.want_plan || (slice_out_alloc(ps.seg, sizeof(mhip_cns_segment), pd.nseg, -1, b.threads) && slice_out_alloc(ps.win, sizeof(mhip_cns_window), pd.nwin, -1, b.threads));
     if (!room) { mhip_set_error("out of memory (%lld windows)", (long long)pd.nwin); return -1; }
-    if ((b.want_pieces || b.want_poa) && pd.nwin > 0 && w.na > 0) {
+    if (b.build_pieces && pd.nwin > 0 && w.na > 0) {
         std::vector<CnsPieceItem> pitems((size_t)w.na);
         std::vector<long long> afl(sl.afirst.begin(), sl.afirst.end());
         parallel_for(nt, b.threads, [&](int64_t tl) {
@@ -404,10 +419,24 @@ int launch_plan(Batch& b, const Slice& sl, SliceWork& w) {
                               pd.nwin, &w.qd)) return -1;
         b.tk[LAP_PLAN_WAIT] += w.qd.wait_s;
         if (b.want_pieces && !slice_out_alloc(ps.pc, sizeof(mhip_cns_piece), w.qd.cap, pd.nwin, b.threads)) { mhip_set_error("out of memory (%lld pieces)", (long long)w.qd.cap); return -1; }
-        if (b.want_poa) {
+        if (b.build_poa) {
             if (cns_poa_launch(c, w.set, w.d_str, w.qd, w.na, (long long)w.a0, pd.d_win, pd.nwin, &w.od)) return -1;
             b.tk[LAP_PLAN_WAIT] += w.od.wait_s; b.poa_large += w.od.nlarge; b.poa_chunks += w.od.nchunks;
-            if (!slice_out_alloc(ps.cn, 1, w.od.cap, pd.nwin, b.threads)) { mhip_set_error("out of memory (%lld bytes of consensus)", (long long)w.od.cap); return -1; }
+            if (b.want_poa && !slice_out_alloc(ps.cn, 1, w.od.cap, pd.nwin, b.threads)) { mhip_set_error("out of memory (%lld bytes of consensus)", (long long)w.od.cap); return -1; }
+        }
+    }
+    if (b.want_reads && pd.nseg > 0) {            // (a segment without a window is a read of its anchors' letters)
+        std::vector<int32_t> rid((size_t)nt, 0);
+        for (int tl = 0; tl < nt; ++tl)
+            if (b.a.tmpl_begin[sl.t0 + tl + 1] > b.a.tmpl_begin[sl.t0 + tl]) rid[(size_t)tl] = b.a.cands[b.a.tmpl_begin[sl.t0 + tl]].sid;
+        if (cns_reads_launch(c, w.set, w.d_tab, w.d_id, nt, sl.t0, tbl.data(), rid.data(), pd.d_seg, pd.nseg, pd.d_segb, b.seg_total, b.win_total, pd.d_win, pd.nwin, w.od.d_cns,
+                             w.od.d_cb, w.od.cap, b.a.min_size, &w.rd)) return -1;
+        b.tk[LAP_PLAN_WAIT] += w.rd.wait_s; b.reads_wait += w.rd.wait_s;
+        ps.t0 = sl.t0; ps.nt = nt;
+        ps.rd.count = w.rd.nreads; ps.sq.count = w.rd.seq_bytes;
+        ps.tbegin.reset((int64_t*)result_alloc(sizeof(int64_t) * ((size_t)nt + 1), b.threads));
+        if (!slice_out_alloc(ps.rd, sizeof(mhip_cns_read), w.rd.nreads, -1, b.threads) || !slice_out_alloc(ps.sq, 1, w.rd.seq_bytes, -1, b.threads) || !ps.tbegin) {
+            mhip_set_error("out of memory (%lld bytes of corrected reads)", (long long)w.rd.seq_bytes); return -1;
         }
     }
     b.seg_total += pd.nseg; b.win_total += pd.nwin;
@@ -424,8 +453,8 @@ int enqueue_copies(Batch& b, const Slice& sl, const SliceWork& w) {
         b.S_used += sl.sbytes;
     }
     const CnsPlanDev& pd = w.pd;
-    if (pd.nseg) HIPCHK(hipMemcpyAsync(w.ps->seg.data.get(), pd.d_seg, sizeof(mhip_cns_segment) * (size_t)pd.nseg, hipMemcpyDeviceToHost, cs));
-    if (pd.nwin) HIPCHK(hipMemcpyAsync(w.ps->win.data.get(), pd.d_win, sizeof(mhip_cns_window) * (size_t)pd.nwin, hipMemcpyDeviceToHost, cs));
+    if (pd.nseg && b.want_plan) HIPCHK(hipMemcpyAsync(w.ps->seg.data.get(), pd.d_seg, sizeof(mhip_cns_segment) * (size_t)pd.nseg, hipMemcpyDeviceToHost, cs));
+    if (pd.nwin && b.want_plan) HIPCHK(hipMemcpyAsync(w.ps->win.data.get(), pd.d_win, sizeof(mhip_cns_window) * (size_t)pd.nwin, hipMemcpyDeviceToHost, cs));
     if (pd.d_bad) HIPCHK(hipMemcpyAsync(&w.ps->win.bad, pd.d_bad, sizeof(long long), hipMemcpyDeviceToHost, cs));      // (b.plan: reserved, nothing moves)
     if (w.qd.d_pb) {                          // (the slots the bound allows; how many hold records is begin[nwin], read at the hand-over)
         SliceOut& pc = w.ps->pc;
@@ -437,9 +466,18 @@ int enqueue_copies(Batch& b, const Slice& sl, const SliceWork& w) {
     }
     if (w.od.d_cb) {                          // (the bytes the bound allows; how many hold strings is begin[nwin], read at the hand-over)
         SliceOut& cn = w.ps->cn;
-        if (w.od.cap) HIPCHK(hipMemcpyAsync(cn.data.get(), w.od.d_cns, (size_t)w.od.cap, hipMemcpyDeviceToHost, cs));
-        HIPCHK(hipMemcpyAsync(cn.begin.get(), w.od.d_cb, sizeof(int64_t) * ((size_t)pd.nwin + 1), hipMemcpyDeviceToHost, cs));
+        if (b.want_poa) {
+            if (w.od.cap) HIPCHK(hipMemcpyAsync(cn.data.get(), w.od.d_cns, (size_t)w.od.cap, hipMemcpyDeviceToHost, cs));
+            HIPCHK(hipMemcpyAsync(cn.begin.get(), w.od.d_cb, sizeof(int64_t) * ((size_t)pd.nwin + 1), hipMemcpyDeviceToHost, cs));
+        }
         HIPCHK(hipMemcpyAsync(&cn.bad, w.od.d_bad, sizeof(long long), hipMemcpyDeviceToHost, cs));
+    }
+    if (w.rd.d_bad) {                         // (exact sizes: cns_reads_launch has waited for the totals)
+        PlanSlice& ps = *w.ps;
+        if (w.rd.nreads) HIPCHK(hipMemcpyAsync(ps.rd.data.get(), w.rd.d_reads, sizeof(mhip_cns_read) * (size_t)w.rd.nreads, hipMemcpyDeviceToHost, cs));
+        if (w.rd.seq_bytes) HIPCHK(hipMemcpyAsync(ps.sq.data.get(), w.rd.d_seq, (size_t)w.rd.seq_bytes, hipMemcpyDeviceToHost, cs));
+        HIPCHK(hipMemcpyAsync(ps.tbegin.get(), w.rd.d_tbegin, sizeof(int64_t) * ((size_t)w.nt + 1), hipMemcpyDeviceToHost, cs));
+        HIPCHK(hipMemcpyAsync(&ps.rd.bad, w.rd.d_bad, sizeof(long long), hipMemcpyDeviceToHost, cs));
     }
     if (w.tw && b.want_tab) {
         HIPCHK(hipMemcpyAsync(b.tab.get() + w.tw0, w.d_tab, sizeof(uint32_t) * (size_t)w.tw, hipMemcpyDeviceToHost, cs));
@@ -453,7 +491,7 @@ int strings_slice(Batch& b, Slice& sl, int set, int k) {
     SliceWork w;
     w.set = set; w.nt = sl.t1 - sl.t0; w.na = (int64_t)sl.items.size();
     w.tw0 = b.build_tab ? b.TB[(size_t)sl.t0] : 0; w.tw = b.build_tab ? b.TB[(size_t)sl.t1] - w.tw0 : 0; w.a0 = b.Avec.size();
-    if (b.want_plan) for (int t = sl.t0; t <= sl.t1; ++t) b.SB[(size_t)t] = b.seg_total;      // (what a slice without a table leaves)
+    if (b.build_plan) for (int t = sl.t0; t <= sl.t1; ++t) b.SB[(size_t)t] = b.seg_total;      // (what a slice without a table leaves)
     if (w.na == 0 && w.tw == 0) return 0;
     if (b.want_str && w.na && reserve_strings(b, sl, k)) return -1;
     std::vector<CnsTabItem> titems;
@@ -463,7 +501,7 @@ int strings_slice(Batch& b, Slice& sl, int set, int k) {
     b.hold_items[set].swap(sl.items); b.hold_titems[set].swap(titems);
     if (w.na && launch_strings(b, sl, w)) return -1;
     if (w.tw && launch_tables(b, sl, w)) return -1;
-    if (b.want_plan && w.tw && launch_plan(b, sl, w)) return -1;
+    if (b.build_plan && w.tw && launch_plan(b, sl, w)) return -1;
     return enqueue_copies(b, sl, w);
 }
 
@@ -473,7 +511,7 @@ template <typename T> CnsBuf<T> copy_of(const T* src, size_t n) {
     return p;
 }
 
-struct PlanResult { CnsBuf<void> seg, win, pc, cn; CnsBuf<int64_t> seg_begin, erange_begin, piece_begin, cns_begin; CnsBuf<int32_t> eranges; };
+struct PlanResult { CnsBuf<void> seg, win, pc, cn, reads, seq; CnsBuf<int64_t> seg_begin, erange_begin, piece_begin, cns_begin, read_begin; CnsBuf<int32_t> eranges; };
 
 // concat_slices over one member of the plan's slices; its refusals in the output's own words (counts: two %lld, no_memory: one)
 struct ConcatTexts { const char *bad, *counts, *no_memory; };
@@ -488,18 +526,60 @@ int concat(Batch& b, SliceOut PlanSlice::*member, size_t elem, CnsBuf<void>* dat
     return rc ? -1 : 0;
 }
 
+// the slices' reads behind one another: the records are final except seq_begin, which gets its batch-wide base here; a template's
+// first record from the slices' tbegin[]
+int put_reads_together(Batch& b, PlanResult& r) {
+    const char* reads_bad = "cns reads: an index left its array, or the letters written are not the letters counted";
+    const size_t n1 = (size_t)b.a.num_templates + 1;
+    if (concat(b, &PlanSlice::rd, sizeof(mhip_cns_read), &r.reads, nullptr, {reads_bad, "", "out of memory (%lld reads)"})) return -1;
+    if (concat(b, &PlanSlice::sq, 1, &r.seq, nullptr, {reads_bad, "", "out of memory (%lld bytes of corrected reads)"})) return -1;
+    r.read_begin.reset((int64_t*)calloc(n1, sizeof(int64_t)));
+    if (!r.read_begin) { mhip_set_error("out of memory"); return -1; }
+    mhip_cns_read* R = (mhip_cns_read*)r.reads.get();
+    int64_t* RB = r.read_begin.get();
+    int64_t rbase = 0, sbase = 0;
+    for (const PlanSlice& p : b.plan) {
+        if (!p.tbegin) continue;
+        const int64_t* tb = p.tbegin.get();
+        bool ok = tb[0] == 0 && tb[p.nt] == p.rd.count;
+        for (int tl = 0; tl < p.nt && ok; ++tl) {
+            ok = tb[tl + 1] >= tb[tl];
+            RB[(size_t)(p.t0 + tl) + 1] = tb[tl + 1] - tb[tl];          // counts -> first record of every template, below
+        }
+        for (int64_t i = 0; i < p.rd.count && ok; ++i) {
+            mhip_cns_read& x = R[rbase + i];
+            ok = x.size > 0 && x.seq_begin >= 0 && x.seq_begin + x.size <= p.sq.count;
+            x.seq_begin += sbase;
+        }
+        if (!ok) { mhip_set_error("%s", reads_bad); return -1; }
+        rbase += p.rd.count; sbase += p.sq.count;
+    }
+    for (size_t t = 0; t + 1 < n1; ++t) RB[t + 1] += RB[t];
+    b.reads_total = rbase; b.seq_total = sbase;
+    return 0;
+}
+
 // the slices' parts of the plan put together (after the last copy has landed)
 int put_plan_together(Batch& b, PlanResult& r) {
     const char* pieces_bad = "cns pieces: an index left its array, or the pieces written are not the pieces counted";
+    const char* poa_bad = "cns poa: a window's graph left its workspace bound, or a piece leaves its backbone";
     const size_t n1 = (size_t)b.a.num_templates + 1;
-    if (concat(b, &PlanSlice::win, sizeof(mhip_cns_window), &r.win, nullptr, {"cns plan: the windows written are not the windows counted", "", "out of memory"})) return -1;
-    if (concat(b, &PlanSlice::seg, sizeof(mhip_cns_segment), &r.seg, nullptr, {"", "", "out of memory"})) return -1;
+    if (b.want_plan) {
+        if (concat(b, &PlanSlice::win, sizeof(mhip_cns_window), &r.win, nullptr, {"cns plan: the windows written are not the windows counted", "", "out of memory"})) return -1;
+        if (concat(b, &PlanSlice::seg, sizeof(mhip_cns_segment), &r.seg, nullptr, {"", "", "out of memory"})) return -1;
+    }
+    for (const PlanSlice& p : b.plan) {        // (the flags come with the stages that were built, copied or not)
+        if (p.win.bad) { mhip_set_error("cns plan: the windows written are not the windows counted"); return -1; }
+        if (p.cn.bad) { mhip_set_error("%s", poa_bad); return -1; }
+    }
     for (const PlanSlice& p : b.plan)          // (the flag comes with POA alone as well)
         if (p.pc.bad) { mhip_set_error("%s", pieces_bad); return -1; }
     if (b.want_pieces && concat(b, &PlanSlice::pc, sizeof(mhip_cns_piece), &r.pc, &r.piece_begin,
                                 {pieces_bad, "cns pieces: inconsistent counts (%lld pieces in %lld slots)", "out of memory (%lld pieces)"})) return -1;
-    if (b.want_poa && concat(b, &PlanSlice::cn, 1, &r.cn, &r.cns_begin, {"cns poa: a window's graph left its workspace bound, or a piece leaves its backbone",
+    if (b.want_poa && concat(b, &PlanSlice::cn, 1, &r.cn, &r.cns_begin, {poa_bad,
                                                                           "cns poa: inconsistent counts (%lld bytes in %lld)", "out of memory (%lld bytes of consensus)"})) return -1;
+    if (b.want_reads && put_reads_together(b, r)) return -1;
+    if (!b.want_plan) return 0;
     for (size_t t = 0; t + 1 < n1; ++t) b.ERB[t + 1] += b.ERB[t];          // counts -> first range of every template
     r.seg_begin = copy_of(b.SB.data(), n1); r.erange_begin = copy_of(b.ERB.data(), n1); r.eranges = copy_of(b.ER.data(), b.ER.size());
     if (!r.seg_begin || !r.erange_begin || !r.eranges) { mhip_set_error("out of memory"); return -1; }
@@ -514,7 +594,7 @@ int hand_over(Batch& b) {
     if (na && !(A = copy_of(b.Avec.data(), (size_t)na))) { mhip_set_error("out of memory"); return -1; }
     if (b.want_tab && !(table_begin = copy_of(b.TB.data(), (size_t)a.num_templates + 1))) { mhip_set_error("out of memory"); return -1; }
     const double t_put = now();
-    const int plan_rc = b.want_plan ? put_plan_together(b, r) : 0;
+    const int plan_rc = b.build_plan ? put_plan_together(b, r) : 0;
     b.tk[LAP_PUT] += now() - t_put;
     if (plan_rc) return -1;
     b.lap(LAP_LAST_COPIES);
@@ -527,7 +607,10 @@ int hand_over(Batch& b) {
         if (b.want_poa)
             fprintf(stderr, "[cns_accept] poa: %lld bytes of consensus, %lld windows in cns_poa_large (%lld launches); the waits for the bounds are counted with the plan's\n",
                     (long long)r.cns_begin.get()[b.win_total], b.poa_large, b.poa_chunks);
-        if (b.want_plan)
+        if (b.want_reads)
+            fprintf(stderr, "[cns_accept] reads: %lld records, %lld bytes of corrected reads: waited for the totals %.3f s (counted with the plan's waits)\n", (long long)b.reads_total,
+                    (long long)b.seq_total, b.reads_wait);
+        if (b.build_plan)
             fprintf(stderr, "[cns_accept] plan: %lld segments, %lld windows: waited for the counts %.3f s (within strings launched), slices' pieces put together %.3f (within last copies)\n",
                     (long long)b.seg_total, (long long)b.win_total, tk[LAP_PLAN_WAIT], tk[LAP_PUT]);
     }
@@ -539,6 +622,7 @@ int hand_over(Batch& b) {
     }
     if (b.want_pieces) { *a.pieces = (mhip_cns_piece*)r.pc.release(); *a.piece_begin = r.piece_begin.release(); }
     if (b.want_poa) { *a.cns = (char*)r.cn.release(); *a.cns_begin = r.cns_begin.release(); }
+    if (b.want_reads) { *a.reads = (mhip_cns_read*)r.reads.release(); *a.read_begin = r.read_begin.release(); *a.seq = (char*)r.seq.release(); *a.seq_bytes = b.seq_total; }
     return 0;
 }
 
@@ -554,7 +638,7 @@ int run(const AcceptCall& a, int allowed) {
         for (int t = 0; t < T; ++t) b.TB[(size_t)t + 1] = b.TB[(size_t)t] + (a.tmpl_begin[t + 1] > a.tmpl_begin[t] ? (int64_t)b.read_size(t) : 0);
     }
     b.TW = b.want_tab ? b.TB[(size_t)T] : 0;
-    if (b.want_plan) { b.SB.assign((size_t)T + 1, 0); b.ERB.assign((size_t)T + 1, 0); }
+    if (b.build_plan) { b.SB.assign((size_t)T + 1, 0); b.ERB.assign((size_t)T + 1, 0); }
     b.lap(LAP_SORT);
     b.jfirst.assign((size_t)T + 1, 0);
     for (int t = 0; t < T; ++t) b.jfirst[(size_t)t + 1] = b.jfirst[(size_t)t] + std::min<int64_t>(b.rules.max_ext, a.tmpl_begin[t + 1] - a.tmpl_begin[t]);
@@ -628,6 +712,17 @@ int mhip_cns_accept_templates_poa(mhip_ctx* c, const mhip_volume* vol, mhip_ext_
     return run({c, vol, cands, tmpl_begin, num_templates, tech, min_align_size, min_mapping_ratio, num_threads, want, min_cov, min_size, out_accepted, out_count, out_strings, out_strings_bytes,
                 out_jobs, out_table, out_ident, out_table_begin, out_segments, out_seg_begin, out_windows, out_n_windows, out_eranges, out_erange_begin, out_pieces, out_piece_begin, out_cns,
                 out_cns_begin}, WANT_STR | WANT_TAB | WANT_PLAN | WANT_PIECES | WANT_POA);
+}
+
+int mhip_cns_accept_templates_reads(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin, int num_templates, int tech, int min_align_size,
+                                    double min_mapping_ratio, int num_threads, int want, int min_cov, int min_size, mhip_cns_accepted** out_accepted, int64_t* out_count, char** out_strings,
+                                    int64_t* out_strings_bytes, int64_t* out_jobs, mhip_cns_table_item** out_table, uint8_t** out_ident, int64_t** out_table_begin,
+                                    mhip_cns_segment** out_segments, int64_t** out_seg_begin, mhip_cns_window** out_windows, int64_t* out_n_windows, int32_t** out_eranges,
+                                    int64_t** out_erange_begin, mhip_cns_piece** out_pieces, int64_t** out_piece_begin, char** out_cns, int64_t** out_cns_begin,
+                                    mhip_cns_read** out_reads, int64_t** out_read_begin, char** out_seq, int64_t* out_seq_bytes) {
+    return run({c, vol, cands, tmpl_begin, num_templates, tech, min_align_size, min_mapping_ratio, num_threads, want, min_cov, min_size, out_accepted, out_count, out_strings, out_strings_bytes,
+                out_jobs, out_table, out_ident, out_table_begin, out_segments, out_seg_begin, out_windows, out_n_windows, out_eranges, out_erange_begin, out_pieces, out_piece_begin, out_cns,
+                out_cns_begin, out_reads, out_read_begin, out_seq, out_seq_bytes}, WANT_STR | WANT_TAB | WANT_PLAN | WANT_PIECES | WANT_POA | WANT_READS);
 }
 
 }  // extern "C"

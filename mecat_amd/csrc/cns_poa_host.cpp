@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "cns_poa.h"
+#include "cns_reads.h"
 
 namespace {
 
@@ -38,6 +39,15 @@ int cns_poa_host_info_words(void) { return CNS_POA_INFO; }
 int cns_poa_host_stats_bytes(void) { return (int)sizeof(CnsPoaStats); }
 int64_t cns_poa_host_words(int64_t nodes, int64_t edges) { return cns_poa_words(nodes, edges); }
 int cns_poa_host_min_weight(int cov) { return cns_poa_min_weight(cov); }
+
+// the corrected reads' record rule (cns_reads.h), the code cns_reads_records runs: records of a target of `size` letters, and block k of
+// a segment [beg, end) as out[4] = L, R, range_beg, range_end
+int64_t cns_reads_host_blocks(int64_t size) { return cns_reads_blocks(size); }
+void cns_reads_host_block(int64_t size, int64_t k, int64_t beg, int64_t end, int64_t* out) {
+    long long L, R, rb, re;
+    cns_reads_block(size, k, beg, end, &L, &R, &rb, &re);
+    out[0] = L; out[1] = R; out[2] = rb; out[3] = re;
+}
 
 // One template: n_alns alignments (alignment a: qaln at buf + off[a], len[a] characters + NUL, saln right behind it), n_windows windows
 // as triples (sb, se, cov), their pieces as records (aln, col, ncols, sb_out), window w owning [piece_begin[w], piece_begin[w + 1]).

@@ -133,6 +133,10 @@ def lib():
     L.mhip_debug_cns_pieces.argtypes = [vp, vp, i64, vp, vp, vp, vp, i32, vp, i32, C.POINTER(vp), C.POINTER(vp)]
     L.mhip_cns_accept_templates_poa.argtypes = L.mhip_cns_accept_templates_pieces.argtypes + [pvp, pvp]
     L.mhip_debug_cns_poa.argtypes = [vp, vp, i64, vp, vp, vp, vp, i32, vp, i32, C.POINTER(vp), C.POINTER(vp)]
+    L.mhip_cns_accept_templates_reads.argtypes = L.mhip_cns_accept_templates_poa.argtypes + [pvp, pvp, pvp, pi64]
+    L.mhip_cns_format_reads.argtypes = [vp, i64, vp, i64, pvp, pi64]
+    L.mhip_debug_cns_reads.argtypes = [vp, vp, vp, vp, i32, vp, vp, i64, vp, i64, vp, vp, i32, pvp, pvp, pvp, pi64]
+    L.mhip_debug_cns_correct.argtypes = [vp, vp, i64, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, pvp, pi64, pvp, pi64]
     L.mhip_cns_poa_small_words.restype = i64
     L.mhip_cns_poa_small_words.argtypes = []
     L.mhip_cns_free.argtypes = [vp]
@@ -530,14 +534,17 @@ def _cns_plan_out(seg, segb, win, nwin, er, erb, ntmpl):
 
 
 def _cns_accept(entry, ctx, vol, cands, tmpl_begin, tech, min_align_size, min_mapping_ratio, want, min_cov=None, min_size=None, threads=8):
-    """the body of the five cns_accept_templates* bindings: mhip_cns_accept_templates + entry ("", "_ex", "_plan", "_pieces", "_poa"), which
-    decides the out-parameters behind out_jobs.  -> (accepted, strings, jobs, table, ident, table_begin, plan dict or None)"""
+    """the body of the six cns_accept_templates* bindings: mhip_cns_accept_templates + entry ("", "_ex", "_plan", "_pieces", "_poa", "_reads"),
+    which decides the out-parameters behind out_jobs.  -> (accepted, strings, jobs, table, ident, table_begin, plan dict or None), and
+    for "_reads" the reads dict or None behind it"""
     cands = np.ascontiguousarray(cands)
     tb = np.ascontiguousarray(tmpl_begin, dtype=np.int64)
     want = int(want)
     acc, st, tab, idn, tbeg, seg, segb, win, er, erb, pc, pcb, cn, cnb = (C.c_void_p() for _ in range(14))
     na, sb, nj, nwin = (C.c_int64() for _ in range(4))
-    outs = [acc, na, st, sb, nj] + [tab, idn, tbeg, seg, segb, win, nwin, er, erb, pc, pcb, cn, cnb][: {"": 0, "_ex": 3, "_plan": 9, "_pieces": 11, "_poa": 13}[entry]]
+    rd, rdb, sq = (C.c_void_p() for _ in range(3))
+    sqb = C.c_int64()
+    outs = [acc, na, st, sb, nj] + [tab, idn, tbeg, seg, segb, win, nwin, er, erb, pc, pcb, cn, cnb, rd, rdb, sq, sqb][: {"": 0, "_ex": 3, "_plan": 9, "_pieces": 11, "_poa": 13, "_reads": 17}[entry]]
     args = [cands.ctypes.data, tb.ctypes.data, len(tb) - 1, tech, min_align_size, float(min_mapping_ratio), threads]
     if entry:
         args += [want] if min_cov is None else [want, int(min_cov), int(min_size)]
@@ -556,7 +563,13 @@ def _cns_accept(entry, ctx, vol, cands, tmpl_begin, tech, min_align_size, min_ma
     if plan is not None and want & CNS_WANT_POA:
         plan["cns_begin"] = _cns_take(cnb, np.int64, int(nwin.value) + 1)
         plan["cns"] = _cns_buffer(cn, int(plan["cns_begin"][-1]) if len(plan["cns_begin"]) else 0)
-    return a, s, nj.value, _cns_buffer(tab, 4 * nw).view(TABLE_DTYPE), _cns_buffer(idn, nw), begin, plan
+    out = (a, s, nj.value, _cns_buffer(tab, 4 * nw).view(TABLE_DTYPE), _cns_buffer(idn, nw), begin, plan)
+    if entry != "_reads":
+        return out
+    if not want & CNS_WANT_READS:
+        return out + (None,)
+    read_begin = _cns_take(rdb, np.int64, len(tb))
+    return out + (dict(reads=_cns_take(rd, READ_DTYPE, int(read_begin[-1]) if len(read_begin) else 0), read_begin=read_begin, seq=_cns_take(sq, np.uint8, sqb.value)),)
 
 
 def cns_accept_templates_plan(ctx, vol, cands, tmpl_begin, tech, min_align_size, min_mapping_ratio, want, min_cov, min_size, threads=8):
@@ -660,6 +673,67 @@ def debug_cns_poa(ctx, buf, off, lens, soff, send, windows):
     _chk(lib().mhip_debug_cns_poa(ctx.h, *args, C.byref(cn), C.byref(cnb)))
     cns_begin = _cns_take(cnb, np.int64, len(keep[-1]) + 1)
     return _cns_take(cn, np.uint8, int(cns_begin[-1])), cns_begin
+
+
+CNS_WANT_READS = 32
+READ_DTYPE = np.dtype([("read_id", np.int32), ("range_beg", np.int32), ("range_end", np.int32), ("size", np.int32), ("seq_begin", np.int64),
+                       ("template_index", np.int32), ("segment", np.int32)])                                            # mhip_cns_read
+assert READ_DTYPE.itemsize == 32
+
+
+def cns_accept_templates_reads(ctx, vol, cands, tmpl_begin, tech, min_align_size, min_mapping_ratio, want, min_cov, min_size, threads=8):
+    """cns_accept_templates_poa with CNS_WANT_READS allowed in `want`, alone or with any other bit: the corrected reads, assembled on the
+    device behind the POA — every segment's target (the anchors' letters and the inner letters of the listed windows' consensus), the
+    min_size filter and output_cns_result's records.  -> cns_accept_templates_poa's tuple + a dict (None without the bit): reads
+    [READ_DTYPE] (template t owns reads[read_begin[t]: read_begin[t + 1]], in segment order then block order; record r owns
+    seq[seq_begin: seq_begin + size]), read_begin [templates + 1], seq [uint8].  With the bit the table, plan, pieces and POA are computed
+    on the device whether or not their bits are set and copied only with them; CNS_WANT_READS alone copies the accepted records and the
+    reads."""
+    return _cns_accept("_reads", ctx, vol, cands, tmpl_begin, tech, min_align_size, min_mapping_ratio, want, min_cov, min_size, threads)
+
+
+def cns_format_reads(reads, seq):
+    """the reference's text of the records (reads_correction_can.cpp:44-46): '>' id '_' range0 '_' range1 '_' size, newline, letters,
+    newline -> bytes"""
+    reads = np.ascontiguousarray(reads, dtype=READ_DTYPE)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    text, n = C.c_void_p(), C.c_int64()
+    _chk(lib().mhip_cns_format_reads(reads.ctypes.data, len(reads), seq.ctypes.data, len(seq), C.byref(text), C.byref(n)))
+    return _cns_take(text, np.uint8, n.value).tobytes()
+
+
+def debug_cns_reads(ctx, table, ident, table_begin, read_ids, segments, windows, cns, cns_begin, min_size):
+    """test hook: the read kernels alone on host-supplied arrays (see mecat_hip.h).  -> dict(reads, read_begin, seq)"""
+    table = np.ascontiguousarray(table, dtype=TABLE_DTYPE)
+    ident = np.ascontiguousarray(ident, dtype=np.uint8)
+    tbeg = np.ascontiguousarray(table_begin, dtype=np.int64)
+    rid = np.ascontiguousarray(read_ids, dtype=np.int32)
+    seg = np.ascontiguousarray(segments, dtype=SEGMENT_DTYPE)
+    win = np.ascontiguousarray(windows, dtype=WINDOW_DTYPE)
+    cns = np.ascontiguousarray(cns, dtype=np.uint8)
+    cb = np.ascontiguousarray(cns_begin, dtype=np.int64)
+    assert len(tbeg) >= 1 and len(table) == len(ident) == tbeg[-1] and len(rid) == len(tbeg) - 1 and len(cb) == len(win) + 1 and len(cns) >= cb[-1]
+    rd, rdb, sq = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    sqb = C.c_int64()
+    _chk(lib().mhip_debug_cns_reads(ctx.h, table.ctypes.data, ident.ctypes.data, tbeg.ctypes.data, len(tbeg) - 1, rid.ctypes.data, seg.ctypes.data, len(seg), win.ctypes.data,
+                                    len(win), cns.ctypes.data, cb.ctypes.data, int(min_size), C.byref(rd), C.byref(rdb), C.byref(sq), C.byref(sqb)))
+    read_begin = _cns_take(rdb, np.int64, len(tbeg))
+    return dict(reads=_cns_take(rd, READ_DTYPE, int(read_begin[-1])), read_begin=read_begin, seq=_cns_take(sq, np.uint8, sqb.value))
+
+
+def debug_cns_correct(ctx, buf, off, lens, soff, send, tmpl_letters, tech, min_cov, min_size, read_id):
+    """test hook: the whole back end on one template — table, plan, pieces, POA, reads — through the accept stage's launchers.  The
+    alignments as debug_cns_pieces takes them, the template's letters as bytes.  -> (reads [READ_DTYPE], seq [uint8])"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    lens, soff, send = (np.ascontiguousarray(x, dtype=np.int32) for x in (lens, soff, send))
+    let = np.frombuffer(bytes(tmpl_letters), dtype=np.uint8)
+    assert len(off) == len(lens) == len(soff) == len(send)
+    rd, sq = C.c_void_p(), C.c_void_p()
+    nr, sqb = C.c_int64(), C.c_int64()
+    _chk(lib().mhip_debug_cns_correct(ctx.h, buf.ctypes.data, len(buf), off.ctypes.data, lens.ctypes.data, soff.ctypes.data, send.ctypes.data, len(off), let.ctypes.data,
+                                      len(let), int(tech), int(min_cov), int(min_size), int(read_id), C.byref(rd), C.byref(nr), C.byref(sq), C.byref(sqb)))
+    return _cns_take(rd, READ_DTYPE, nr.value), _cns_take(sq, np.uint8, sqb.value)
 
 
 COMM_ID_BYTES = 128
