@@ -78,8 +78,8 @@ clean:
 dwstats: $(LIBDIR)/libmecat_hip_dwstats.so
 $(LIBDIR)/libmecat_hip_dwstats.so: $(HIP_SRCS) $(HIP_HDRS)
 	@mkdir -p build/dwstats $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -DMECAT_DW_STATS -x hip -c $(CSRC)/align.hip -o build/dwstats/align.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC build/dwstats/align.o $(filter-out build/align.o,$(HIP_OBJS)) -o $@
+	$(HIPCC) $(HIPFLAGS) -DMECAT_DW_STATS -x hip -c $(CSRC)/dw_extend2.hip -o build/dwstats/dw_extend2.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC build/dwstats/dw_extend2.o $(filter-out build/dw_extend2.o,$(HIP_OBJS)) -o $@
 
 # development variant with the index build's section clocks compiled in (tools/dev/idx_time.py with MECAT_HIP_LIB set)
 ixstats: $(LIBDIR)/libmecat_hip_ixstats.so

@@ -9,7 +9,7 @@
 //     ...50          at most 50 candidates per read instead of 100 (:23)
 // On the device (C ABI, include/mecat_hip.h): the look-up table with bucket cap 256 (mhip_index_build_ex), seeding + candidate
 // selection (mhip_asm_seed_reads_ex, asm_seed.hip), the O(ND) extension of every candidate in both directions (mhip_asm_extend_run /
-// _fetch, cns_align.hip: the columns come back packed, into page-locked buffers).  On the host, per candidate and on -T threads: what the tool does with the two aligned string pairs afterwards —
+// _fetch, asm_extend.hip: the columns come back packed, into page-locked buffers).  On the host, per candidate and on -T threads: what the tool does with the two aligned string pairs afterwards —
 // string_check's gap shuffling of the left pair (:199-281), the overlap of the two directions on the seed 13-mer, coordinates, the
 // 450-base test, jscore and the 12-field line (:843-948).  Line order inside the .r files is by read here and by thread timing in the
 // tool: the consumer (mecat2asmpwConvert) reads lines one by one.

@@ -3,11 +3,11 @@
 // The re-aligner needs the whole edit path of every block (the consensus stage consumes the aligned strings), and rounds 1-4 kept it the
 // way the reference does: every d-row's furthest-x values, 2 bytes per cell, written to a per-wave scratch and read back by a traceback
 // that one whole wave walked step by step — 113 GB written per launch for 442 k jobs, one unit per wave, a fifth of dw_extend2's rate.
-// Now the forward rows ARE dw_extend2 (align.hip, instantiated with mecat2cns' block rules: two units per wave, d-rows in a 1 K-entry LDS
+// Now the forward rows ARE dw_extend2 (dw_extend2.hip, instantiated with mecat2cns' block rules: two units per wave, d-rows in a 1 K-entry LDS
 // ring, tail walk for the cut in front of the last four matches), and what it keeps of a row is what a traceback cannot recompute: ONE
 // BIT per cell — "came from diagonal k - 1" — plus the row's width and the cut of the band update behind it: a 16-byte record per row
 // (CnsRowRec) instead of ~54 bytes.  The path itself is found afterwards, for all blocks of all units at once, by cns_trace
-// (cns_align.hip): one LANE per block walks the bits back from the block's end point, then walks the path forward again, re-measuring
+// (cns_trace.hip): one LANE per block walks the bits back from the block's end point, then walks the path forward again, re-measuring
 // every snake on the packed reads (an O(ND) path has no mismatch columns: a row is one indel and a run of equal bases), and writes the
 // 2-bit columns.  13 M independent blocks per config-2 pass keep every lane of the chip busy; nothing waits for a scalar walk.
 #pragma once
@@ -47,5 +47,5 @@ struct CnsFwdArgs {
     int* err_flag;                 // a direction needed more than dir_cols_cap columns
 };
 
-// align.hip: the forward pass over jobs [0, n) (both directions of each), on the context's stream
+// dw_extend2.hip: the forward pass over jobs [0, n) (both directions of each), on the context's stream
 int cns_forward_launch(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads, const void* d_jobs, int n, const CnsFwdArgs& args);

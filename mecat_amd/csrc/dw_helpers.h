@@ -1,4 +1,5 @@
-// dw_helpers.h — device helpers shared by the O(ND) aligners (align.hip: mecat2pw's dw; cns_align.hip: mecat2cns' dw):
+// dw_helpers.h — device helpers shared by the O(ND) aligners (dw_extend.hip, dw_extend2.hip: mecat2pw's dw and mecat2cns' forward rows;
+// cns_extend.hip, cns_trace.hip: mecat2cns' and mecat2asmpw's paths):
 // views of a read as the aligner walks it (forward / backward, complemented), 16-base windows of the packed volume and of
 // LDS-staged blocks, packed snake comparison, wave64 DPP reductions.
 #pragma once
@@ -46,16 +47,6 @@ __device__ __forceinline__ uint32_t view_word_le(const SeqView& s, int i0) {
         w = lo >= 0 ? pac_win16(s.pac, lo) : (pac_win16(s.pac, 0) >> ((-lo) << 1));
     }
     return s.comp ? ~w : w;
-}
-// ({hi, lo} << s) >> 32 for s in 0..30, branch-free (HIP's __funnelshift_l lowers to a divergent branch on s == 0)
-__device__ __forceinline__ uint32_t funnel_l(uint32_t lo, uint32_t hi, int s) {
-    const uint32_t r = __builtin_amdgcn_alignbit(hi, lo, (32 - s) & 31);
-    return s ? r : hi;
-}
-// 16 bases of a staged block starting at base x
-__device__ __forceinline__ uint32_t lds_win16(const uint32_t* P, int x) {
-    const int w = x >> 4;
-    return funnel_l(P[w + 1], P[w], (x & 15) << 1);      // ({P[w], P[w+1]} << s) >> 32
 }
 
 // number of leading equal bases (0..32) of the 32-base windows at Q[x..] and T[y..].  Qp/Tp carry one leading pad
@@ -124,15 +115,6 @@ __device__ __forceinline__ int match16_le(const uint32_t* Q, int x, const uint32
     uint32_t tz;                                        // v_ffbl_b32 of 0 is -1: 16 equal bases read as 0x7fffffff
     asm("v_ffbl_b32 %0, %1" : "=v"(tz) : "v"(d));
     return (int)(tz >> 1);
-}
-__device__ __forceinline__ int match32_le(const uint32_t* Q, int x, const uint32_t* T, int y) {
-    const int wq = x >> 4, wt = y >> 4;
-    const uint32_t sq = (uint32_t)(x + x), st = (uint32_t)(y + y);
-    const uint32_t q0 = Q[wq], q1 = Q[wq + 1], q2 = Q[wq + 2], t0 = T[wt], t1 = T[wt + 1], t2 = T[wt + 2];
-    const uint32_t dl = __builtin_amdgcn_alignbit(q1, q0, sq) ^ __builtin_amdgcn_alignbit(t1, t0, st);
-    const uint32_t dh = __builtin_amdgcn_alignbit(q2, q1, sq) ^ __builtin_amdgcn_alignbit(t2, t1, st);
-    const int nl = dl ? (__builtin_ctz(dl) >> 1) : 16, nh = dh ? 16 + (__builtin_ctz(dh) >> 1) : 32;
-    return dl ? nl : nh;
 }
 
 // ---- wave64 reductions on the DPP network (no LDS traffic): quad swaps, half-row / row mirrors, row broadcasts.

@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "aln_jobs.h"
 #include "common.h"
 #include "scan.h"
 
@@ -1051,29 +1052,7 @@ int mhip_xalign_candidates_dev(mhip_ctx* c, const mhip_volume* ref, const mhip_v
 
 int mhip_xalign_candidates(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads, const mhip_aln_job* jobs, int n,
                            int min_align_size, mhip_aln_result* out) {
-    HIPCHK(hipSetDevice(c->device));
-    if (n <= 0) return 0;
-    for (int i = 0; i < n; ++i) {
-        const mhip_aln_job& j = jobs[i];
-        if (j.qid_local < 0 || j.qid_local >= reads->num_reads || j.sid_local < 0 || j.sid_local >= ref->num_reads) {
-            mhip_set_error("alignment job %d: read index out of range", i);
-            return -1;
-        }
-        const int qs = reads->h_offs[(size_t)j.qid_local].size, ts = ref->h_offs[(size_t)j.sid_local].size;
-        if (j.qstart > qs || j.sstart > ts) {      // (a negative start point is a job without extension)
-            mhip_set_error("alignment job %d: start point outside the reads", i);
-            return -1;
-        }
-    }
-    mhip_aln_job* d_jobs;
-    mhip_aln_result* d_out;
-    if (c->scratch("al_jobs", sizeof(mhip_aln_job) * (size_t)n, (void**)&d_jobs)) return -1;
-    if (c->scratch("al_out", sizeof(mhip_aln_result) * (size_t)n, (void**)&d_out)) return -1;
-    HIPCHK(hipMemcpyAsync(d_jobs, jobs, sizeof(mhip_aln_job) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    if (mhip_xalign_candidates_dev(c, ref, reads, d_jobs, n, min_align_size, d_out)) return -1;
-    HIPCHK(hipMemcpyAsync(out, d_out, sizeof(mhip_aln_result) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    return aln_jobs_run(c, ref, reads, jobs, n, min_align_size, out, mhip_xalign_candidates_dev);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // valu_peak — calibrates the instruction-issue ceilings that bench.py prices the dw kernel against.
 //
-// The d-path kernels (align.hip) are integer VALU work on LDS-resident state; their HBM fraction is tiny by construction
+// The d-path kernels (dw_extend2.hip, dw_extend.hip) are integer VALU work on LDS-resident state; their HBM fraction is tiny by construction
 // (SURVEY.md §8d), so the interpretable ceiling is the rate at which the chip issues wave64 instructions.  This program
 // measures that rate on the device it runs on, per instruction class, for 1, 2, 4 and 8 resident waves per SIMD: eight
 // independent register streams per wave, 64 instructions per loop iteration.  Output: one JSON object on stdout, rates in

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Last step of a round's profile: ties the committed PMC summaries to the kernel sources they were measured on.
 
-    python profiles/finish.py r02 [/tmp/align.s]
+    python profiles/finish.py r02 [/tmp/dw_extend2.s]
 
 Writes <tag>_pmc_source.json = {"kernel_source_digest": sha256 over mecat_amd/csrc/* (bench.py: src_digest), ...} — bench.py quotes
 `roofline.traffic` and the instruction counts of <tag>_hbm_traffic.json / <tag>_instruction_mix.json only while the digest equals
@@ -25,11 +25,11 @@ def main():
             "tool": "rocprofv3 --kernel-trace --stats / --pmc (separate passes), tools/dev/profile_bench.sh"}
     # (dw_extend2ILb0 = the <false> instantiation, mecat2pw's aligner: up to round 5 the first function whose name holds "dw_extend2" was taken,
     # which is the <true> instantiation — mecat2cns' forward pass with its row log — since that one exists)
-    asm = sys.argv[2] if len(sys.argv) > 2 else "/tmp/align_%s.s" % tag
+    asm = sys.argv[2] if len(sys.argv) > 2 else "/tmp/dw_extend2_%s.s" % tag
     if not os.path.exists(asm):
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"),
                         "-I" + os.path.join(ROOT, "mecat_amd", "csrc"), "-S", "--cuda-device-only", "-x", "hip",
-                        os.path.join(ROOT, "mecat_amd", "csrc", "align.hip"), "-o", asm], check=True, stderr=subprocess.DEVNULL)
+                        os.path.join(ROOT, "mecat_amd", "csrc", "dw_extend2.hip"), "-o", asm], check=True, stderr=subprocess.DEVNULL)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_mix.py"), asm, "dw_extend2ILb0"], stdout=subprocess.PIPE, text=True, check=True).stdout
     m = re.search(r"valu 4-cycle share: ([0-9.]+)", out)
     p = os.path.join(HERE, "%s_instruction_mix.json" % tag)

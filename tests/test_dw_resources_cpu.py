@@ -29,7 +29,7 @@ def _hipflags():
 def compiled(tmp_path_factory):
     out = tmp_path_factory.mktemp("dwres") / "align.s"
     r = subprocess.run([HIPCC] + _hipflags() + ["-x", "hip", "--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage",
-                                                os.path.join("mecat_amd", "csrc", "align.hip"), "-o", str(out)],
+                                                os.path.join("mecat_amd", "csrc", "dw_extend2.hip"), "-o", str(out)],
                        cwd=ROOT, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     return r.stderr, open(out).read()

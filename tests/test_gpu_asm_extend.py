@@ -1,5 +1,5 @@
 """SURVEY.md §8f row N3, the extension of mecat2canu's overlappers at function level: mhip_asm_extend, mhip_asm_extend_run and
-mhip_asm_extend_fetch (mecat_amd/csrc/cns_align.hip: cns_extend<true>, ae_word_offsets, ae_pack) against tests/golden/asm_ext.npz — the
+mhip_asm_extend_fetch (mecat_amd/csrc/asm_extend.hip: ae_word_offsets, ae_pack; cns_extend.hip: cns_extend<true>) against tests/golden/asm_ext.npz — the
 aligned strings the UNMODIFIED pairwise_mapping of mecat2asmpw.c left for every candidate (oracle/ref_harness_asmpw_ext.c,
 tests/golden/make_golden_asm_ext.py), turned into the header's five counts per direction and its 2-bit columns.  Read sets: the golden
 2 % set with either block indexed, corrected reads at 4 / 5 / 6 % and at 10 / 12 % error (only the last two make `align`'s limit of 0.10

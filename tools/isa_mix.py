@@ -10,7 +10,7 @@ Classes follow the issue costs measured by mecat_amd/bin/valu_peak on gfx950 (pr
 Also reports `vcc_rereads`: v_cndmask reads of VCC beyond the first after each write of VCC (the slow pattern: a chain of
 selects on one compare through VCC issues 2-4x slower than through an SGPR pair).
 
-    python tools/isa_mix.py build/align.s dw_extend2 [--ops] [--row-loops]
+    python tools/isa_mix.py build/dw_extend2.s dw_extend2 [--ops] [--row-loops]
 
 --row-loops: only the basic blocks of dw_extend2's d-row loops — the depth-2 loops (LLVM's loop annotations in the assembly) that
 contain the half-wave row maximum (v_permlane16_swap), with the snake loops nested in them; set-up, tail traceback and accounting
