@@ -16,10 +16,13 @@
 // stay traceable; the rare block whose tail traceback needs an overwritten row, or that never reached an end of either sequence,
 // is handed over to the one-unit kernel (dw_extend), which keeps every row: 0.5 % of the units.
 // Snake steps compare 16 bases per v_alignbit pair on blocks staged little-endian (view_word_le); one-pass (58 %) and two-pass rows
-// have loop bodies of their own.  64 VGPRs, 19 KB of LDS per four waves, eight waves per SIMD (tests/test_dw_resources_cpu.py holds the
-// compiler to it); per average dual row 78 VALU + 45 SALU, issue-bound cycle for cycle (profiles/r03_dw_row_breakdown.md,
-// r05_dw_attempt.md).  The row loops are frozen; the code between two row loops is 10 % of a wave's life
-// (profiles/dw_block_setup.md).
+// have loop bodies of their own.  Inside a block the row code keeps positions in doubled units (2 x is its own v_alignbit shift operand),
+// counts the rows of the two fast loops on the scalar unit, and takes the band update's first diagonal and slot count from the scalar
+// unit as one packed word per half (profiles/dw_row_trims.md); the code around the row loops works in base units.
+// 64 VGPRs, 19 KB of LDS per four waves, eight waves per SIMD (tests/test_dw_resources_cpu.py holds the compiler to it); a one-pass
+// dual row is 48 VALU (146 issue cycles) + 27 SALU, a two-pass row 81 (248) + 48 (tests/test_dw_row_cycles_cpu.py caps the cycles);
+// VALU-issue bound (profiles/r03_dw_row_breakdown.md, r05_dw_attempt.md).  The code between two row loops is 10 % of a wave's life
+// (profiles/dw_block_setup.md).  What is and is not settled about the row loops: DESIGN.md §6.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -45,7 +48,7 @@ struct HalfLds {
     uint32_t Qp[SEQ_WORDS2];
     uint32_t Tp[SEQ_WORDS2];
 };
-// The ring of d-rows of a half: 16-bit rows packed back to back, wrapping (in front of row 0: -1, 0, -1, see the block set-up).
+// The ring of d-rows of a half: 16-bit rows of doubled x packed back to back, wrapping (in front of row 0: -2, 0, -2, see the block set-up).
 // It is its own 2 KB-aligned LDS array so that the address of ring byte position p is `base | (p & 0x7fe)`: one v_and_or_b32.
 // Positions (lin, pbase, rlin) are kept in bytes.
 typedef __attribute__((address_space(3))) uint16_t lds_u16_t;
@@ -141,8 +144,9 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
     q.pac = qpac; t.pac = rpac; q.off = 0; t.off = 0; q.A = q.B = t.A = t.B = 0; q.comp = t.comp = 0;
     int query_size = 0, target_size = 0, qidx = 0, tidx = 0;
     int Rq = 0, Rt = 0, Rm = 0, Rc = 0, Rb = 0;
-    // per-half block state
-    int qblk = 0, tblk = 0, last_block = 0, band_tol = 0, max_d = 0;
+    // per-half block state.  The block's two lengths and its band tolerance are kept in the row loops' doubled units (`2`, see below) and
+    // halved where the code around the loops wants them: kept in both forms they would cost three registers across the row loops.
+    int q_len2 = 0, t_len2 = 0, last_block = 0, band_tol2 = 0, max_d = 0;
     // band = nslot diagonals from min_k; d = rows done.  The three values every lane adds its own 2 * sl to on every row are kept with
     // it added (`_l`: per lane): the row code then uses them as they are, and the band update moves all lanes by the same amount.
     int best_m = -1, mk_l = 0, nslot = 0, aligned = 0, end_x = 0, end_k = 0, end_d = 0, end_mk = 0, d = 0;
@@ -171,7 +175,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 unsigned int u = 0;
                 if (sl == 0) u = atomicAdd(cursor, 1u);
                 u = __shfl(u, hh << 5);
-                if (u >= 2u * (unsigned)n) { exhausted = true; setup = false; mk_l = 2 * sl; nslot = 0; dlim = 0; }      // never rowing
+                if (u >= 2u * (unsigned)n) { exhausted = true; setup = false; mk_l = 4 * sl; nslot = 0; dlim = 0; }      // never rowing
                 else {
                     unit = u;
                     const mhip_aln_job jb = jobs[u >> 1];
@@ -194,6 +198,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
             // ---- 2. block setup: retrieve_next_aln_block (gapalign.cpp:9-45) + staging
             if (setup) {
                 const int qleft = query_size - qidx, tleft = target_size - tidx;
+                int qblk, tblk, band_tol;
                 if (CNS) {      // dw_in_one_direction, dw.cpp:319-332
                     const int ext = min(qleft, tleft);
                     if (ext > SEG_BLK + 100) { qblk = SEG_BLK; last_block = 0; } else { qblk = max(ext, 0); last_block = 1; }
@@ -232,19 +237,24 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 }
                 // The reference zero-fills V per block (:232-233); row d only reads diagonals written by row d - 1, except row 0,
                 // which reads V[k_offset - 1] and V[k_offset + 1]: the two zeros in front of row 0.
-                // Between two rows of the ring sits one entry of -1 (see the start point below); in front of row 0: -1, 0, -1 — row 0 reads
-                // the first two (x = max(-1 + 1, 0) = 0), row 1 reads the third as the entry "left of row 0".
-                if (sl < 3) ring_st(rbase, 2u * sl, sl == 1 ? 0 : -1);
-                best_m = -1; mk_l = 2 * sl; nslot = 1; sepv = ~1; cut = 0;
+                // Between two rows of the ring sits one entry of -2 or less (see the start point below); in front of row 0: -2, 0, -2 — row 0
+                // reads the first two (x2 = max(-2 + 2, 0) = 0), row 1 reads the third as the entry "left of row 0".
+                if (sl < 3) ring_st(rbase, 2u * sl, sl == 1 ? 0 : -2);
+                best_m = -2; mk_l = 4 * sl; nslot = 1; sepv = ~1; cut = 0;
                 aligned = 0; end_x = 0; end_k = 0; end_d = 0; d = 0;
                 lin_l = 6u + 2u * sl; pb_l = 2u * sl; rlin_l = 2u * sl;
                 dlim = max_d; inblock = true;
+                q_len2 = 2 * qblk; t_len2 = 2 * tblk; band_tol2 = 2 * band_tol;
                 setup = false;
             }
             __builtin_amdgcn_wave_barrier();
         }
         if (!BALLOT(!exhausted)) break;
-        const int q_len = qblk, t_len = tblk, k_offset = max_d;
+        const int k_offset = max_d;
+        // Inside a block the row code keeps positions in doubled units (`2`: x2 = 2 x, y2 = 2 y, diagonal k2 = 2 k; with them x + y of
+        // the band threshold, best_m and mk_l): a position is then its own v_alignbit shift operand (match16_le2).  Ring entries are
+        // x2 (at most 2 * 736 = 1472: still 16 bits, and the entries between rows stay negative); ring positions, cut, slot counts, the
+        // row log and `cells` are what they were, and everything behind the end-of-block scan is in base units again.
         DWS_T(t_b);
         DWS_ADD(tk_setup, t_a, t_b);
 
@@ -266,25 +276,36 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
             // the row maximum qualifies, and the row maximum is the running maximum (x + y grows by at least one per row along
             // the best path, which the band never prunes).
             int first, last;
+            int pk = 0;      // BOTH, NJ <= 2: (new slot count | first << 8) of the lane's half, which is the next row's separator but for a NOT
             if (NJ == 1) {
                 // 32 diagonals per half: one ballot; first / last set bit of the half's 32 bits with the raw instructions
                 // (v_ffbl / v_ffbh return -1 for an empty mask: a half without a block, whose values are not used)
-                const unsigned long long q0 = BALLOT(m0 >= best_m - band_tol);
-                const unsigned int m32 = (unsigned int)(q0 >> (hh << 5));
-                int lz;
-                asm("v_ffbl_b32 %0, %1" : "=v"(first) : "v"(m32));
-                asm("v_ffbh_u32 %0, %1" : "=v"(lz) : "v"(m32));
-                last = 31 - lz;
+                const unsigned long long q0 = BALLOT(m0 >= best_m - band_tol2);      // (both sides doubled: the same predicate)
                 if (BOTH) {
+                    // the scalar unit finds first and the new slot count of both halves anyway: it hands them to the lanes packed, one
+                    // word per half in a register pair, and a lane takes its half's word with the one 64-bit shift that used to fetch
+                    // the half's ballot bits (then: two find-bit instructions, an add and a subtract per row on the vector unit)
                     const unsigned int wa = (unsigned int)q0, wb = (unsigned int)(q0 >> 32);
-                    sa = 33 - (__builtin_ctz(wa) + __builtin_clz(wa));
-                    sb = 33 - (__builtin_ctz(wb) + __builtin_clz(wb));
+                    const int fa = __builtin_ctz(wa), fb = __builtin_ctz(wb);
+                    sa = 33 - (fa + __builtin_clz(wa));
+                    sb = 33 - (fb + __builtin_clz(wb));
+                    unsigned long long pkw = (unsigned int)(sa | (fa << 8)) | ((unsigned long long)(unsigned int)(sb | (fb << 8)) << 32);
+                    asm("" : "+s"(pkw));
+                    pk = (int)(unsigned int)(pkw >> (hh << 5));
+                    first = pk >> 8;
+                    last = first + (pk & 0xff) - 2;
+                } else {
+                    const unsigned int m32 = (unsigned int)(q0 >> (hh << 5));
+                    int lz;
+                    asm("v_ffbl_b32 %0, %1" : "=v"(first) : "v"(m32));
+                    asm("v_ffbh_u32 %0, %1" : "=v"(lz) : "v"(m32));
+                    last = 31 - lz;
                 }
             } else if (NJ == 2) {
                 // up to 64 diagonals per half: two ballots, the half's 2 x 32 qualification bits.  Branch-free: v_ffbl / v_ffbh return
                 // -1 for an empty word, which `| 32` leaves at 0xffffffff (first: unsigned min) and `^ 31` turns into -32 (last:
                 // signed max; x ^ 31 == 31 - x for x in 0..31)
-                const int thr = best_m - band_tol;
+                const int thr = best_m - band_tol2;
                 const unsigned long long q0 = BALLOT(mp >= thr), q1 = BALLOT(m0 >= thr);
                 if (BOTH) {
                     // first / last qualifying diagonal of each half on the scalar unit (its 64 bits: the half's word of both ballots),
@@ -295,11 +316,12 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                     const int la = 63 - __builtin_clzll(wa), lb = 63 - __builtin_clzll(wb);
                     sa = la - fa + 2;
                     sb = lb - fb + 2;
-                    int pka = fa | (sa << 8), pkb = fb | (sb << 8);          // (first, new slot count: last = first + slots - 2)
-                    asm("" : "+s"(pka), "+s"(pkb));                          // (kept packed: the compiler would select the four values one by one)
-                    const int pk = hh ? pkb : pka;
-                    first = pk & 0xff;
-                    last = first + (pk >> 8) - 2;
+                    // (new slot count, first: last = first + slots - 2; kept packed: the compiler would select the four values one by one)
+                    unsigned long long pkw = (unsigned int)(sa | (fa << 8)) | ((unsigned long long)(unsigned int)(sb | (fb << 8)) << 32);
+                    asm("" : "+s"(pkw));
+                    pk = (int)(unsigned int)(pkw >> (hh << 5));
+                    first = pk >> 8;
+                    last = first + (pk & 0xff) - 2;
                 } else {
                     const unsigned int lo32 = (unsigned int)(q0 >> (hh << 5)), hi32 = (unsigned int)(q1 >> (hh << 5));
                     unsigned int fl, fh, ll, lh;
@@ -315,25 +337,32 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 for (int j = 0; j < NJ; ++j) {
                     const int tt = sl + 32 * j;
                     const bool act = inblock && tt < nslot;
-                    const int k = mk_l + 64 * j;
-                    const int u = act ? 2 * ring_ld(rbase, rlin_l + 64u * (unsigned)j) - k : -0x40000000;
-                    if (act && u >= best_m - band_tol) { lo = min(lo, tt); hi = max(hi, tt); }
+                    const int k2 = mk_l + 128 * j;
+                    const int u = act ? 2 * ring_ld(rbase, rlin_l + 64u * (unsigned)j) - k2 : -0x40000000;      // x2 + y2 = 2 x2 - k2
+                    if (act && u >= best_m - band_tol2) { lo = min(lo, tt); hi = max(hi, tt); }
                 }
                 first = half_min(lo); last = half_max(hi);
             }
             if (BOTH || inblock) {
                 // new band [min_k + 2 first - 1, min_k + 2 last + 1] = last - first + 2 diagonals; the previous-row entry of diagonal
                 // (new min_k) - 1 sits at ring position rlin + first - 1
-                pb_l = rlin_l + 2u * (unsigned)(first - 1);
+                // (mk_l in doubled units: + 4 first - 2.  2 first is formed once, by add — a shift left issues at half the rate —, and
+                // 2 first - 2 serves both updates)
+                const unsigned int first2 = twice((unsigned)first), step = first2 - 2u;
+                pb_l = rlin_l + step;
                 nslot = last - first + 2;
-                mk_l = mk_l + 2 * first - 1;
+                mk_l = mk_l + (int)first2 + (int)step;
                 cut = first;
-                // what the idle lanes of the next row store behind it: its slot count and this cut (7 bits, saturating: the tail
-                // traceback hands a block over when it meets 127), as a negative 16-bit number — which is all the start point needs
-                // of the entry between two rows
-                int c7;
-                asm("v_min_u16 %0, 0x7f, %1" : "=v"(c7) : "v"(first));
-                sepv = ~(nslot | (c7 << 8));
+                // what the idle lanes of the next row store behind it: its slot count and this cut, as a negative 16-bit number — which is
+                // all the start point needs of the entry between two rows.  With both halves in a row of one or two passes that is the
+                // packed word, inverted (a cut below 64).  Otherwise the cut is kept to 7 bits, saturating: the tail traceback hands a
+                // block over when it meets 127.
+                if (BOTH && NJ <= 2) sepv = ~pk;
+                else {
+                    int c7;
+                    asm("v_min_u16 %0, 0x7f, %1" : "=v"(c7) : "v"(first));
+                    sepv = ~(nslot | (c7 << 8));
+                }
             }
             if (!(BOTH && NJ <= 2)) { sa = __builtin_amdgcn_readlane(nslot, 0); sb = __builtin_amdgcn_readlane(nslot, 32); }
         };
@@ -341,16 +370,16 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
         unsigned int row_bytes = 0;
         // One d-row of both halves in NJ passes of 32 diagonals per half (NJ a constant for 1 and 2: the pass loop and the previous-pass
         // bookkeeping fold away).  ns_a / ns_b: the two halves' slot counts on the scalar unit.  A row is followed in the ring by one
-        // entry of -1, which the first idle lane of the last pass writes: every lane of a pass stores (its x, or -1 when idle) at its
-        // own position — no exec juggling around the store, no store of its own for the -1 (unless a half fills its last pass to the
-        // last lane: the caller's business, see `full` below).  What idle lanes write beyond the -1 is overwritten by the rows that
+        // negative entry (sepv), which the first idle lane of the last pass writes: every lane of a pass stores (its x, or sepv when idle) at
+        // its own position — no exec juggling around the store, no store of its own for that entry (unless a half fills its last pass to the
+        // last lane: the caller's business, see `full` below).  What idle lanes write beyond it is overwritten by the rows that
         // follow, except for up to 64 entries behind the last row of a block with NJ <= 2: the tail traceback's window is shortened
         // by as much (rows with more passes guard their stores).  FAST 1: 1 <= slots <= 32 in both halves, one pass; FAST 2: 1 <= slots
         // <= 63, two passes; FAST 0: anything.
         auto row_passes = [&](const int NJ, const int ns_a, const int ns_b, auto fast_tag) __attribute__((always_inline)) {
             constexpr int FAST = decltype(fast_tag)::value;
 
-            row_bytes = 2u * (unsigned)nslot + 2u;
+            row_bytes = twice((unsigned)nslot) + 2u;
             last_ns = nslot;
             int mmax = -0x40000000, m0 = -0x40000000, mp = -0x40000000;
             unsigned long long e = 0;
@@ -369,24 +398,25 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                     amask = clamped_bits_at<0>(ns_a - 32 * j) | clamped_bits_at<32>(ns_b - 32 * j);
                 }
                 const bool act = __builtin_amdgcn_inverse_ballot_w64(amask);
-                const int k = mk_l + 64 * j;
+                const int k2 = mk_l + 128 * j;                          // (doubled: lane offset 4 sl, 128 per pass)
                 const unsigned int rp = pb_l + 64u * (unsigned)j;       // idle lanes read (and ignore) whatever the ring holds there
                 const int vl = ring_ld(rbase, rp), vr = ring_ld(rbase, rp + 2u);
-                // :138-142 `if (k == min_k || (k != max_k && V[k-1] < V[k+1])) x = V[k+1]; else x = V[k-1] + 1;` as max(vl + 1, vr):
-                // inside the band the two are the same thing (vl < vr <=> vr >= vl + 1).  At k == min_k the entry on the left is either
-                // the -1 between two rows (vl + 1 = 0 <= vr) or a diagonal of row d - 1 that the band update dropped while its right
-                // neighbour stayed: 2 vl - (k - 1) < best - tol <= 2 vr - (k + 1), i.e. vl + 1 < vr; mirrored at k == max_k (vr is -1, or
-                // a dropped diagonal with vr < vl + 1).  So the two edge tests fold into the same max — in the 16-bit forms of add and
-                // max, which issue at twice the rate of the 32-bit max (the result is >= 0 and comes back zero-extended).
-                int x;
+                // :138-142 `if (k == min_k || (k != max_k && V[k-1] < V[k+1])) x = V[k+1]; else x = V[k-1] + 1;` as max(vl + 1, vr), in
+                // doubled units max(vl + 2, vr): inside the band the two are the same thing (vl < vr <=> vr >= vl + 1).  At k == min_k the
+                // entry on the left is either the entry between two rows — ~(nslot | cut << 8) with nslot >= 1, hence <= -2: vl + 2 <= 0 <=
+                // vr — or a diagonal of row d - 1 that the band update dropped while its right neighbour stayed: 2 vl - (k - 1) < best - tol
+                // <= 2 vr - (k + 1) in base units, i.e. vl + 1 < vr; mirrored at k == max_k (vr is negative, or a dropped diagonal with
+                // vr < vl + 1).  So the two edge tests fold into the same max — in the 16-bit forms of add and max, which issue at twice the
+                // rate of the 32-bit max (the result is >= 0 and comes back zero-extended).
+                int x;                           // x2 (and y, lim, nn, m0 below: y2, 2 lim, 2 nn, 2 (x + y))
                 {
                     int v1;
-                    asm("v_add_u16 %0, 1, %1" : "=v"(v1) : "v"(vl));
+                    asm("v_add_u16 %0, 2, %1" : "=v"(v1) : "v"(vl));
                     asm("v_max_i16 %0, %1, %2" : "=v"(x) : "v"(v1), "v"(vr));
                     if (CNS) {
                         // the step the reference's traceback will read off V (dw.cpp:176-179: from k + 1 when k == min_k, or k != max_k and
                         // V[k - 1] < V[k + 1]): with the entries the ring holds at a band's two edges (see above) that is "vl >= vr"
-                        // everywhere, i.e. vl + 1 > vr: one 16-bit compare of what is in registers anyway (idle lanes: masked by the reader,
+                        // everywhere, i.e. vl + 1 > vr (doubled: vl + 2 > vr): one 16-bit compare of what is in registers anyway (idle lanes: masked by the reader,
                         // which knows the row's slots)
                         unsigned long long fb;
                         asm("v_cmp_gt_i16_e64 %0, %1, %2" : "=s"(fb) : "v"(v1), "v"(vr));
@@ -399,11 +429,11 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 }
                 // 0 <= y <= t_len and x <= q_len on every live diagonal (a diagonal at an end stops the block); idle lanes sit
                 // at (q_len, 0), where lim == 0
-                x = act ? x : q_len;
+                x = act ? x : q_len2;
                 // (idle lanes: lim <= 0 whatever y is, so they never move forward and never ask for another step; their window
                 // loads may fall outside the staged block or outside the LDS allocation, where reads return 0: nothing of an
                 // idle lane is kept — the stored value, the end mask and m0 below are all guarded by `act`)
-                int y = x - k;
+                int y = x - k2;
                 int lim, nn;
 #ifdef MECAT_DW_STATS
                 snake2 -= 1;
@@ -412,13 +442,13 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
 #ifdef MECAT_DW_STATS
                     snake2 += 1;
 #endif
-                    lim = min(q_len - x, t_len - y);
-                    // 0..15 equal bases, or >= 16 (0x7fffffff) when the whole window matches.  A lane with exactly 16 bases left
-                    // that all match asks for one more step, which then moves nothing.
-                    const int m = match16_le(S.Qp, x, S.Tp, y);
-                    asm("v_min3_i32 %0, %1, %2, 16" : "=v"(nn) : "v"(m), "v"(lim));
+                    lim = min(q_len2 - x, t_len2 - y);
+                    // 0..15 equal bases (doubled: 0..30), or >= 16 (0x7ffffffe) when the whole window matches.  A lane with exactly 16
+                    // bases left that all match asks for one more step, which then moves nothing.
+                    const int m = match16_le2(S.Qp, x, S.Tp, y);
+                    asm("v_min3_i32 %0, %1, %2, 32" : "=v"(nn) : "v"(m), "v"(lim));
                     x += nn; y += nn;
-                } while (BALLOT(nn == 16));
+                } while (BALLOT(nn == 32));
                 if (NJ <= 2 || tt <= nslot) ring_st(rbase, lin_l + 64u * (unsigned)j, act ? x : sepv);
                 // nothing left of the query or of the target on this diagonal
                 e |= BALLOT(lim == nn) & amask;
@@ -476,17 +506,21 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
             // (d < dlim in both) as one count-down, the band-size limits (:118 "max_k - min_k <= band_size") of the two halves next to
             // the slot counts, which are on the scalar unit anyway.  One-pass rows run in a loop of their own.
             int rows_left = min(__builtin_amdgcn_readlane(dlim - d, 0), __builtin_amdgcn_readlane(dlim - d, 32));
-            const int lim_a = __builtin_amdgcn_readlane(band_tol, 0) + 1, lim_b = __builtin_amdgcn_readlane(band_tol, 32) + 1;
+            const int lim_a = (__builtin_amdgcn_readlane(band_tol2, 0) >> 1) + 1, lim_b = (__builtin_amdgcn_readlane(band_tol2, 32) >> 1) + 1;
             const int one_a = min(lim_a, 32), one_b = min(lim_b, 32);
             const int two_a = min(lim_a, 63), two_b = min(lim_b, 63);
             typedef std::integral_constant<int, 0> fast0;
             typedef std::integral_constant<int, 1> fast1;
             typedef std::integral_constant<int, 2> fast2;
+            // Both halves advance by the same rows here and nothing in the loops reads d: the rows are counted on the scalar unit and
+            // added to d once behind the loops (a per-lane d += go is a v_addc per row).
+            int rows_run = 0;
             while (true) {
                 // one-pass rows (rows left, and both slot counts within their limits: one sign test)
                 while (((rows_left - 1) | (one_a - ns_a) | (one_b - ns_b)) >= 0) {
                     DWS_ROW(~0ull, ns_a, ns_b, 1);
                     rows_left -= 1;
+                    rows_run += 1;
                     const bool full = ((ns_a | ns_b) & 32) != 0;       // a half has all of its 32 lanes on diagonals: nobody stores the entry
                     row_passes(1, ns_a, ns_b, fast1{});                //   behind its row (the other half's idle lane rewrites its own)
                     lin_l += row_bytes;
@@ -495,9 +529,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                     log_row(1, std::true_type{});
                     // (a row that reached an end leaves the loop through its bound: a second exit makes the compiler build a machine of
                     // flag registers and re-tested branches around every row)
-                    const int go = ended ? 0 : 1;
-                    rows_left = go ? rows_left : -1;
-                    d += go;
+                    rows_left = ended ? -1 : rows_left;
                     __builtin_amdgcn_wave_barrier();
                 }
                 if (ended) break;
@@ -506,13 +538,12 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                     DWS_ROW(~0ull, ns_a, ns_b, 2);
                     NJ = 2;
                     rows_left -= 1;
+                    rows_run += 1;
                     row_passes(2, ns_a, ns_b, fast2{});
                     band_update(2, last_m0, last_mp, std::true_type{}, ns_a, ns_b);
                     log_row(2, std::true_type{});
                     lin_l += row_bytes;
-                    const int go = ended ? 0 : 1;
-                    rows_left = go ? rows_left : -1;
-                    d += go;
+                    rows_left = ended ? -1 : rows_left;
                     __builtin_amdgcn_wave_barrier();
                 }
                 if (ended) break;
@@ -521,6 +552,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 if (ns_max < 64) continue;                   // back to the two loops above
                 // a half with 64 slots or more (0.01 % of the rows): the general form
                 rows_left -= 1;
+                rows_run += 1;
                 NJ = (ns_max + 31) >> 5;
                 DWS_ROW(~0ull, ns_a, ns_b, NJ);
                 row_passes(NJ, ns_a, ns_b, fast0{});
@@ -529,15 +561,17 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 band_update(NJ, last_m0, last_mp, std::true_type{}, ns_a, ns_b);
                 log_row(NJ, std::true_type{});
                 if (ended) break;
-                d += 1;
                 __builtin_amdgcn_wave_barrier();
             }
+            // every exit of the loop comes by here: a row that reached an end is not counted (the end-of-block code below counts it)
+            d += rows_run - (ended ? 1 : 0);
         } else {
             // one half is between blocks (or out of units) while the other one rows on: the general form of everything
+            const int slot_lim = (band_tol2 >> 1) + 1;
             while (true) {
                 // the two conditions as masks (a ballot of their conjunction makes the compiler turn the mask into a 0/1 vector and
                 // compare it again)
-                const unsigned long long rmask = BALLOT(d < dlim) & BALLOT(nslot <= band_tol + 1);
+                const unsigned long long rmask = BALLOT(d < dlim) & BALLOT(nslot <= slot_lim);
                 if (rmask != inmask) break;
                 const int ns_max = max(ns_a, ns_b);
                 NJ = (ns_max + 31) >> 5;
@@ -562,12 +596,14 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
             // lowest diagonal that reached an end (:168-169), from the row just stored.  The band update for the row after it has been
             // done already (the other half goes on with it): the band of the end row is what that update started from — its slots
             // from the row's length in the ring, its first diagonal from the cut.
-            const int en = (int)((lin_l - rlin_l) >> 1) - 1, emk_l = mk_l - 2 * cut + 1;
+            // (mk_l is in doubled units and even: halved, it is the base-unit value the rest of the block's code works with)
+            const int en = (int)((lin_l - rlin_l) >> 1) - 1, emk_l = (mk_l >> 1) - 2 * cut + 1;
+            const int q_len = q_len2 >> 1, t_len = t_len2 >> 1;
             int hkey = 0x7fffffff;
             for (int j = 0; BALLOT(sl + 32 * j < en); ++j) {
                 const int k = emk_l + 64 * j, kk = k + k_offset;
                 if (sl + 32 * j < en) {
-                    const int x = ring_ld(rbase, rlin_l + 64u * (unsigned)j);
+                    const int x = ring_ld(rbase, rlin_l + 64u * (unsigned)j) >> 1;      // (base units: hkey has ten bits for it)
                     if (x >= q_len || x - k >= t_len) hkey = min(hkey, (kk << 10) | x);
                 }
             }
@@ -580,7 +616,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
             d += 1;
             __builtin_amdgcn_wave_barrier();
         }
-        row_ok = d < dlim && nslot <= band_tol + 1;
+        row_ok = d < dlim && nslot <= (band_tol2 >> 1) + 1;
         DWS_T(t_d);
         DWS_ADD(tk_ended, t_c, t_d);
 
@@ -592,8 +628,8 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
         bool handover = !CNS && fin && d > 0 && !aligned;
         const int end_y = end_x - end_k;
         const int aln_size = (end_x + end_y + end_d) / 2;
-        int cd = end_d, ck = end_k, cx2 = end_x;
-        int acnt = 0, found = 0;
+        int cd = end_d, ck = end_k, cx2 = 2 * end_x;      // cx2, acnt2: the walk's x and its column count in doubled units, like the ring's entries
+        int acnt2 = 0, found = 0;
         bool tracing = CNS ? (has_aln && !last_block) : has_aln;      // (CNS: a last block keeps all of its columns, dw.cpp:353-358)
         // Rows are walked back over the entries between them: behind row r sits ~(slots of r | left cut of row r - 1 << 8).  clin / cmin:
         // ring position and first diagonal of row cd (the row that reached the end is the row that ran last); sepc: the entry behind row
@@ -607,7 +643,8 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
             if (tracing) {
                 // The path came to (cx2, diagonal ck) of row cd from diagonal ck - 1 (vl, one query base) or ck + 1 (vr, one target base)
                 // of row cd - 1 and then ran along the snake from x1: x1 = max(vl + 1, vr), from the right when vl < vr, and the point it
-                // left row cd - 1 at is x = max(vl, vr).  A neighbour outside row cd - 1 counts as -1, which is all the reference's edge
+                // left row cd - 1 at is x = max(vl, vr).  The walk's x values are doubled, as the ring holds them: + 1 is + 2, a run of four is
+                // 8, and the counts are halved behind the loop.  A neighbour outside row cd - 1 counts as -1 (-2), which is all the reference's edge
                 // tests (k == min_k: from the right; k == max_k: from the left) do: inside row cd - 1 but outside the band that row cd
                 // was cut to, the left neighbour of min_k has vl + 1 < vr and the right neighbour of max_k vr < vl + 1 (see row_passes).
                 // One straight line of selects (nested conditions cost a copy of every carried value per branch); in row 0 (cd == 0:
@@ -624,13 +661,13 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 // each against the row's last offset
                 const unsigned int ol = (unsigned)(ck - 1 - pmin), olast = 2u * (unsigned)pns - 2u;
                 const int rl = ring_ld(rbase, plin + ol), rr = ring_ld(rbase, plin + ol + 2u);
-                const int vl = ol <= olast ? rl : -1, vr = ol + 2u <= olast ? rr : -1;
-                const int x1 = up ? max(vl + 1, vr) : 0;
+                const int vl = ol <= olast ? rl : -2, vr = ol + 2u <= olast ? rr : -2;      // (-1 in doubled units)
+                const int x1 = up ? max(vl + 2, vr) : 0;
                 const int sn = cx2 - x1;
-                const bool run4 = sn >= 4;                       // the run of four matches: the walk ends in front of it
+                const bool run4 = sn >= 8;                       // the run of four matches: the walk ends in front of it
                 const bool go = up && !run4 && !lost;            // otherwise one more row back (in row 0 there is none: no run found)
-                acnt += run4 ? 4 : sn + (up ? 1 : 0);
-                cx2 = run4 ? cx2 - 4 : (up ? max(vl, vr) : 0);
+                acnt2 += run4 ? 8 : sn + (up ? 2 : 0);
+                cx2 = run4 ? cx2 - 8 : (up ? max(vl, vr) : 0);
                 ck = go ? ck + (vl < vr ? 1 : -1) : ck;
                 cd -= go ? 1 : 0;
                 found = run4 ? 1 : 0;
@@ -639,12 +676,15 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 tracing = go;
             }
         }
-        // query / target bases the walk took off the end of the alignment: it stands at (cx2, diagonal ck)
-        int qcnt = end_x - cx2, tcnt = end_y - (cx2 - ck);
+        // query / target bases the walk took off the end of the alignment: it stands at (cx, diagonal ck)
+        const int cx = cx2 >> 1;
+        int acnt = acnt2 >> 1;
+        int qcnt = end_x - cx, tcnt = end_y - (cx - ck);
         const int trim_ok = has_aln && found && (aln_size - acnt >= 2);
         DWS_T(t_e);
         DWS_ADD(tk_trace, t_d, t_e);
 
+        const int qblk = q_len2 >> 1, tblk = t_len2 >> 1;
         // ---- 5. block accounting (dw_in_one_direction, diff_gapalign.cpp:259-290); a block this kernel cannot finish (0.07 %: the
         // tail needs a row that left the ring, or no end was reached) hands the unit over to dw_extend, which redoes that block
         // and the rest of the unit with every row kept

@@ -103,18 +103,34 @@ __device__ __forceinline__ uint32_t unflip_symbols(uint32_t word, uint32_t plane
     return word ^ m;
 }
 
+// 2 x as v_add_u32 x, x (written out: the optimizer turns x + x into a shift left, and on this chip a shift left occupies the SIMD
+// for 4 cycles where the plain 32-bit add takes 2 — DESIGN.md §3.3, valu_peak)
+__device__ __forceinline__ uint32_t twice(uint32_t x) {
+    uint32_t r;
+    asm("v_add_u32 %0, %1, %1" : "=v"(r) : "v"(x));
+    return r;
+}
+
 // little-endian staged blocks (view_word_le; no pad word: base i lives in word i >> 4)
 __device__ __forceinline__ int match16_le(const uint32_t* Q, int x, const uint32_t* T, int y) {
     const int wq = x >> 4, wt = y >> 4;
-    // the shift operands 2x and 2y as v_add_u32 x, x (written out: the optimizer turns x + x into a shift left, and on this chip a
-    // shift left occupies the SIMD for 4 cycles where the plain 32-bit add takes 2 — DESIGN.md §3.3, valu_peak)
-    uint32_t sx, sy;
-    asm("v_add_u32 %0, %1, %1" : "=v"(sx) : "v"(x));
-    asm("v_add_u32 %0, %1, %1" : "=v"(sy) : "v"(y));
+    const uint32_t sx = twice((uint32_t)x), sy = twice((uint32_t)y);      // the shift operands 2x and 2y
     const uint32_t d = __builtin_amdgcn_alignbit(Q[wq + 1], Q[wq], sx) ^ __builtin_amdgcn_alignbit(T[wt + 1], T[wt], sy);
     uint32_t tz;                                        // v_ffbl_b32 of 0 is -1: 16 equal bases read as 0x7fffffff
     asm("v_ffbl_b32 %0, %1" : "=v"(tz) : "v"(d));
     return (int)(tz >> 1);
+}
+
+// match16_le on positions in doubled units (x2 = 2 x, y2 = 2 y; dw_extend2's row loops): the window's word is x2 >> 5 and x2 itself is
+// the v_alignbit shift operand (2 x modulo 32), so the two adds of match16_le go.  The result is in doubled units too: the bit index of
+// the first difference with its lowest bit cleared (2 * (tz >> 1)); the sign bit is cleared with it, so that 16 equal bases (v_ffbl_b32
+// of 0 is -1) still read as a large positive number, 0x7ffffffe.  Callers clamp with min3(.., lim2, 32).
+__device__ __forceinline__ int match16_le2(const uint32_t* Q, int x2, const uint32_t* T, int y2) {
+    const int wq = x2 >> 5, wt = y2 >> 5;
+    const uint32_t d = __builtin_amdgcn_alignbit(Q[wq + 1], Q[wq], (uint32_t)x2) ^ __builtin_amdgcn_alignbit(T[wt + 1], T[wt], (uint32_t)y2);
+    uint32_t tz;
+    asm("v_ffbl_b32 %0, %1" : "=v"(tz) : "v"(d));
+    return (int)(tz & 0x7ffffffeu);
 }
 
 // ---- wave64 reductions on the DPP network (no LDS traffic): quad swaps, half-row / row mirrors, row broadcasts.
