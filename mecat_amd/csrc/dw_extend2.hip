@@ -157,7 +157,10 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
     unsigned int rlin_l = 0;    // ring position of the row that ran last, + 2 sl
     int dlim = 0;               // rows run while d < dlim: max_d of the block, 0 once an end was reached / without a block
     // CNS: the unit's share of the row log [logpos, logend), the record of the current block's row 0, and whether the unit met something
-    // the log cannot hold (a row of more than 64 diagonals, a cut of 127 or more, more rows than its share): such a unit is handed over
+    // the log cannot hold: more rows than its share, or a row of more than 96 diagonals (a record holds three passes of 32; the pass count is
+    // the wave's, so a fourth pass for the other half's row sends this half's unit along).  Such a unit is handed over to cns_extend, like
+    // one whose tail walk left the ring or met a cut of 127 or more, or whose block records are used up
+    // (tests/test_gpu_cns_forward_edges.py: rows of 96 diagonals stay, wider ones leave).
     unsigned int logpos = 0, logend = 0, blk_log0 = 0, blkpos = 0, blkend = 0;
     bool cns_bad = false;
     unsigned long long fl0 = 0, fl1 = 0, fl2 = 0;      // lanes whose diagonal came from k - 1, first / second / third pass of the row that ran last
