@@ -1,8 +1,10 @@
 # Top-level build.  `make all` = everything that can be built on this machine.
 #   hip     mecat_amd/lib/libmecat_hip.so   HIP kernels + C-ABI (gfx950)
 #           mecat_amd/lib/libcns_poa_host.so   the POA window routine (csrc/cns_poa.h) compiled for the host, no HIP: the tests' expected values
-#                                              and the corrected reads' record rule (csrc/cns_reads.h), the function the record kernel runs
+#                                              and the corrected reads' record rule (csrc/cns_reads.h), the function the record kernel runs,
+#                                              and their text's header rule (csrc/cns_text.h), the function the text kernel runs
 #   host    mecat_amd/bin/mecat2pw          C++ host driver (drop-in CLI) on top of the C-ABI
+#           mecat_amd/bin/mecat2cns         the consensus program (drop-in CLI) on top of the C-ABI
 #   synth   mecat_amd/lib/libsynth.so + mecat_amd/bin/synth_reads   synthetic read generator
 #   oracle  oracle/liboracle.so             CPU restatement (test infrastructure)
 #   ref     oracle/_ref/*                   unmodified reference (only where /root/reference exists)
@@ -24,7 +26,7 @@ all: synth oracle hip host
 	@if [ -d /root/reference/src ]; then $(MAKE) ref; fi
 
 hip: $(LIBDIR)/libmecat_hip.so $(LIBDIR)/libcns_poa_host.so
-$(LIBDIR)/libcns_poa_host.so: $(CSRC)/cns_poa_host.cpp $(CSRC)/cns_poa.h $(CSRC)/cns_reads.h
+$(LIBDIR)/libcns_poa_host.so: $(CSRC)/cns_poa_host.cpp $(CSRC)/cns_poa.h $(CSRC)/cns_reads.h $(CSRC)/cns_text.h
 	@mkdir -p $(LIBDIR)
 	$(CXX) -O2 -std=c++17 -fPIC -shared -Wall -I$(CSRC) $< -o $@
 build/%.o: $(CSRC)/%.hip $(HIP_HDRS)
@@ -34,7 +36,7 @@ $(LIBDIR)/libmecat_hip.so: $(HIP_OBJS)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(HIP_OBJS) -o $@
 
-host: $(BINDIR)/mecat2pw $(BINDIR)/mecat2cns_partition $(BINDIR)/valu_peak $(BINDIR)/gather_peak $(BINDIR)/mecat2asmpw
+host: $(BINDIR)/mecat2pw $(BINDIR)/mecat2cns_partition $(BINDIR)/valu_peak $(BINDIR)/gather_peak $(BINDIR)/mecat2asmpw $(BINDIR)/mecat2cns
 # issue-rate calibration for bench.py's dw roofline (measures, computes nothing of the path)
 $(BINDIR)/valu_peak: mecat_amd/tools/valu_peak.hip
 	@mkdir -p $(BINDIR)
@@ -52,6 +54,12 @@ $(BINDIR)/mecat2asmpw: mecat_amd/asmpw/asmpw_main.cpp include/mecat_hip.h $(LIBD
 	@mkdir -p $(BINDIR)
 	$(CXX) -O3 -std=c++17 -pthread -Wall -Iinclude mecat_amd/asmpw/asmpw_main.cpp -L$(LIBDIR) -lmecat_hip -Wl,-rpath,'$$ORIGIN/../lib' -o $@
 	for n in mecat2trimpw mecat2asmpw50 mecat2trimpw50; do cp -f $@ $(BINDIR)/$$n; done
+
+# mecat2cns itself (drop-in CLI): the partition step, the reads as one resident volume, one mhip_cns_correct_templates call per partition file
+CNS_SRCS := mecat_amd/cns/cns_main.cpp mecat_amd/host/volume.cpp mecat_amd/host/partition.cpp
+$(BINDIR)/mecat2cns: $(CNS_SRCS) mecat_amd/cns/cns_groups.h $(wildcard mecat_amd/host/*.h) include/mecat_hip.h $(LIBDIR)/libmecat_hip.so
+	@mkdir -p $(BINDIR)
+	$(CXX) -O2 -std=c++17 -pthread -Wall -Iinclude $(CNS_SRCS) -L$(LIBDIR) -lmecat_hip -Wl,-rpath,'$$ORIGIN/../lib' -o $@
 
 $(BINDIR)/mecat2cns_partition: mecat_amd/tools/partition_main.cpp mecat_amd/host/partition.cpp mecat_amd/host/partition.h
 	@mkdir -p $(BINDIR)

@@ -406,7 +406,7 @@ int  mhip_debug_cns_table(mhip_ctx* ctx, const char* buf, int64_t bytes, const i
  *                      anchor i to the next anchor j (the segment's end if there is none) the window (sb = i, se = j) is listed when some
  *                      position of [i, j) has UNDS or FDEL — these are the stretches the reference hands to meap_cns_one_indel, with
  *                      cov = mat_cnt + ins_cnt at i as its min_cov (:103).  Positions in front of the first anchor belong to no window.
- * The mecat2cns defaults are min_cov 4 / min_size 5000 (PacBio) and 6 / 2000 (nanopore); min_size >= 2 and min_cov >= 1 are required.
+ * The mecat2cns defaults are min_cov 6 / min_size 5000 (PacBio) and 6 / 2000 (nanopore); min_size >= 2 and min_cov >= 1 are required.
  * Segments come in template order, then ascending beg: template t owns out_segments[out_seg_begin[t] .. out_seg_begin[t + 1]).  Windows
  * come in segment order, then ascending sb: segment s owns out_windows[win_begin .. win_end).  Effective ranges are (start, end) pairs:
  * template t owns pairs out_erange_begin[t] .. out_erange_begin[t + 1].  The output is the same bytes on every run.
@@ -579,6 +579,49 @@ int  mhip_debug_cns_reads(mhip_ctx* ctx, const mhip_cns_table_item* table, const
 int  mhip_debug_cns_correct(mhip_ctx* ctx, const char* buf, int64_t bytes, const int64_t* off, const int32_t* len, const int32_t* soff,
                             const int32_t* send, int n_pairs, const char* tmpl_letters, int tmpl_len, int tech, int min_cov, int min_size,
                             int read_id, mhip_cns_read** out_reads, int64_t* out_n_reads, char** out_seq, int64_t* out_seq_bytes);
+/* ---- the corrected reads' FASTA text (cns_text.hip) and the entry point of the mecat2cns program (mecat_amd/cns/cns_main.cpp).
+ * The text is the reference's (reads_correction_can.cpp:44-46; mhip_cns_format_reads above is the same text made on the host), made on
+ * the device behind a slice's read kernels: a record's length is 1 + digits(read_id) + 1 + digits(range_beg) + 1 + digits(range_end) +
+ * 1 + digits(size) + 1 + size + 1, the positions are a prefix sum, and a wave per record writes the header (lane l computes character l:
+ * csrc/cns_text.h, one function for the kernel and for libcns_poa_host.so) and copies the letters with 16-byte stores.  A cut segment's
+ * target is stored once on the device; the text repeats the overlapping stretches, so the duplication happens there and the host never
+ * walks the output.  Records are in template order and slices hold whole templates: the slices' texts are concatenated as they are.
+ * mhip_cns_correct_templates takes its options and outputs as structs instead of another 38 arguments:
+ *   opts->tech, min_align_size, min_mapping_ratio, num_threads, min_cov, min_size   as in mhip_cns_accept_templates_reads
+ *   opts->want          the MHIP_CNS_WANT_* bits, MHIP_CNS_WANT_TEXT among them
+ *   opts->input_type    0: the walk of consensus_one_read_can_* (cands[] sorted by score in place, as in every entry point above).
+ *                       1: the walk of consensus_one_read_m4_* (mecat_correction.cpp:241-360): a template's records are its overlaps, in
+ *                       the order given.  With at most max_added of them (60 PacBio, 100 nanopore) every one is aligned, in that order;
+ *                       with more, the template's range of cands[] is sorted in place with std::sort by max(qend - qoff, send - soff)
+ *                       descending (CompareOverlapByOverlapSize, no tie-break: the same call on the same bytes gives the reference's
+ *                       order) and the first max_added are aligned.  An overlap is accepted when GetAlignment succeeds and, for
+ *                       nanopore only, check_ovlp_mapping_range with min_mapping_ratio - 0.02 holds; there is no used-ids set, no
+ *                       coverage check and no limit of 200.  Everything behind the accept decisions is the same code.
+ * With input_type 0 and `want` without MHIP_CNS_WANT_TEXT the call is mhip_cns_accept_templates_reads, byte for byte.  With
+ * MHIP_CNS_WANT_TEXT the table, plan, pieces, POA and reads are computed on the device whether or not their bits are set, and each is
+ * copied to the host only with its own bit: MHIP_CNS_WANT_TEXT alone moves the accepted records and the text over the PCIe link, nothing
+ * else — in particular not the letters (out->seq stays NULL).  The host waits once more per slice, for the text's total.  The entry
+ * points above keep refusing the bit.  Every member of *out is set (NULL / 0 where not asked for); release them with
+ * mhip_cns_outputs_free, which leaves the struct zeroed (the members may also be released one by one with mhip_cns_free). */
+#define MHIP_CNS_WANT_TEXT 64
+typedef struct { int tech, input_type /* 0 .can walk, 1 m4 walk */, min_align_size, min_cov, min_size, num_threads, want; double min_mapping_ratio; } mhip_cns_opts;
+typedef struct {
+    mhip_cns_accepted* accepted; int64_t count; char* strings; int64_t strings_bytes; int64_t jobs;
+    mhip_cns_table_item* table; uint8_t* ident; int64_t* table_begin /* [num_templates + 1] */;
+    mhip_cns_segment* segments; int64_t* seg_begin /* [num_templates + 1] */; mhip_cns_window* windows; int64_t n_windows;
+    int32_t* eranges; int64_t* erange_begin /* [num_templates + 1] */;
+    mhip_cns_piece* pieces; int64_t* piece_begin /* [n_windows + 1] */;
+    char* cns; int64_t* cns_begin /* [n_windows + 1] */;
+    mhip_cns_read* reads; int64_t* read_begin /* [num_templates + 1] */; char* seq; int64_t seq_bytes;
+    char* text; int64_t text_bytes;      /* no terminator */
+} mhip_cns_outputs;
+int  mhip_cns_correct_templates(mhip_ctx* ctx, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin, int num_templates,
+                                const mhip_cns_opts* opts, mhip_cns_outputs* out);
+void mhip_cns_outputs_free(mhip_cns_outputs* out);
+/* test hook: the text kernels alone on n host-supplied records whose letters are seq[seq_begin .. seq_begin + size).  Refused before
+ * anything is launched: a record that leaves seq[0 .. seq_bytes), a negative read_id, range_beg, range_end or size.
+ * -> *out_text (malloc'ed, no terminator, release with mhip_cns_free), *out_bytes; n == 0 gives 0 bytes */
+int  mhip_debug_cns_text(mhip_ctx* ctx, const mhip_cns_read* reads, int64_t n, const char* seq, int64_t seq_bytes, char** out_text, int64_t* out_bytes);
 /* mhip_cns_free does not return a string buffer to the system at once: the library keeps the LARGEST released one (gigabytes — about
  * 14 GB for a config-2-sized batch) and hands it out again to the next batch that fits, because first-touching fresh pages costs
  * more than the batch's GPU time.  The parked buffer belongs to the process, not to a context (mhip_ctx_destroy leaves it).  This call

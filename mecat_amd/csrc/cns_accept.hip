@@ -26,6 +26,9 @@
 // mhip_cns_accept_templates_poa adds the POA consensus of every listed window (meap_cns_one_indel, :62-78) — cns_poa.hip — and
 // mhip_cns_accept_templates_reads what the reference ends with: every segment's target put together from the anchors' letters and the
 // windows' strings (:88-107), the size filter and output_cns_result's records (:233, :155-188), behind a slice's consensus — cns_reads.hip.
+// mhip_cns_correct_templates is the entry point of the mecat2cns program: the same stages with the options and outputs in two structs,
+// the walk of consensus_one_read_m4_* (:241-360) as a second rule set in front of the strings (input_type 1: cns_replay.h), and the
+// FASTA text of the records made on the device behind a slice's read kernels (reads_correction_can.cpp:44-46) — cns_text.hip.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -47,10 +50,11 @@
 #include "cns_slices.h"
 #include "cns_strings.h"
 #include "cns_table.h"
+#include "cns_text.h"
 
 namespace {
 
-const int WANT_STR = MHIP_CNS_WANT_STRINGS, WANT_TAB = MHIP_CNS_WANT_TABLE, WANT_PLAN = MHIP_CNS_WANT_PLAN, WANT_PIECES = MHIP_CNS_WANT_PIECES, WANT_POA = MHIP_CNS_WANT_POA, WANT_READS = MHIP_CNS_WANT_READS;
+const int WANT_STR = MHIP_CNS_WANT_STRINGS, WANT_TAB = MHIP_CNS_WANT_TABLE, WANT_PLAN = MHIP_CNS_WANT_PLAN, WANT_PIECES = MHIP_CNS_WANT_PIECES, WANT_POA = MHIP_CNS_WANT_POA, WANT_READS = MHIP_CNS_WANT_READS, WANT_TEXT = MHIP_CNS_WANT_TEXT;
 
 struct CmpByScore {      // CmpExtensionCandidateByScore, mecat_correction.cpp:362-370
     bool operator()(const mhip_ext_candidate& a, const mhip_ext_candidate& b) const {
@@ -69,6 +73,7 @@ struct AcceptCall {
     mhip_cns_segment** segments = nullptr; int64_t** seg_begin = nullptr; mhip_cns_window** windows = nullptr; int64_t* n_windows = nullptr; int32_t** eranges = nullptr; int64_t** erange_begin = nullptr;
     mhip_cns_piece** pieces = nullptr; int64_t** piece_begin = nullptr; char** cns = nullptr; int64_t** cns_begin = nullptr;
     mhip_cns_read** reads = nullptr; int64_t** read_begin = nullptr; char** seq = nullptr; int64_t* seq_bytes = nullptr;
+    int input_type = 0; char** text = nullptr; int64_t* text_bytes = nullptr;      // (mhip_cns_correct_templates only)
 };
 
 template <typename T> void clear_out(T* p) { if (p) *p = T(); }
@@ -77,8 +82,9 @@ template <typename T> void clear_out(T* p) { if (p) *p = T(); }
 int validate(const AcceptCall& a, int allowed) {
     const int want = a.want;
     const char *plan = (allowed & WANT_PLAN) ? " | MHIP_CNS_WANT_PLAN" : "", *pieces = (allowed & WANT_PIECES) ? " | MHIP_CNS_WANT_PIECES" : "", *poa = (allowed & WANT_POA) ? " | MHIP_CNS_WANT_POA" : "";
-    const char* reads = (allowed & WANT_READS) ? " | MHIP_CNS_WANT_READS" : "";
-    if (want == 0 || (want & ~allowed)) { mhip_set_error("cns accept: want = %d (MHIP_CNS_WANT_STRINGS | MHIP_CNS_WANT_TABLE%s%s%s%s)", want, plan, pieces, poa, reads); return -1; }
+    const char *reads = (allowed & WANT_READS) ? " | MHIP_CNS_WANT_READS" : "", *text = (allowed & WANT_TEXT) ? " | MHIP_CNS_WANT_TEXT" : "";
+    if (want == 0 || (want & ~allowed)) { mhip_set_error("cns accept: want = %d (MHIP_CNS_WANT_STRINGS | MHIP_CNS_WANT_TABLE%s%s%s%s%s)", want, plan, pieces, poa, reads, text); return -1; }
+    if (a.input_type != 0 && a.input_type != 1) { mhip_set_error("cns accept: input_type = %d (0: the .can walk, 1: the m4 walk)", a.input_type); return -1; }
     if ((want & WANT_PIECES) && !(want & WANT_PLAN)) { mhip_set_error("cns accept: want = %d: MHIP_CNS_WANT_PIECES needs MHIP_CNS_WANT_PLAN (pieces belong to the plan's windows)", want); return -1; }
     if ((want & WANT_POA) && !(want & WANT_PLAN)) { mhip_set_error("cns accept: want = %d: MHIP_CNS_WANT_POA needs MHIP_CNS_WANT_PLAN (the consensus belongs to the plan's windows)", want); return -1; }
     if ((want & WANT_POA) && (!a.cns || !a.cns_begin)) { mhip_set_error("cns accept: the consensus was asked for without a place to put it"); return -1; }
@@ -86,11 +92,12 @@ int validate(const AcceptCall& a, int allowed) {
     if ((want & WANT_TAB) && (!a.table || !a.ident || !a.table_begin)) { mhip_set_error("cns accept: the table was asked for without a place to put it"); return -1; }
     if ((want & WANT_PLAN) && (!a.segments || !a.seg_begin || !a.windows || !a.n_windows || !a.eranges || !a.erange_begin)) { mhip_set_error("cns accept: the plan was asked for without a place to put it"); return -1; }
     if ((want & WANT_READS) && (!a.reads || !a.read_begin || !a.seq || !a.seq_bytes)) { mhip_set_error("cns accept: the reads were asked for without a place to put them"); return -1; }
-    if ((want & (WANT_PLAN | WANT_READS)) && (a.min_size < 2 || a.min_cov < 1)) { mhip_set_error("cns accept: the plan needs min_size >= 2 and min_cov >= 1 (%d, %d)", a.min_size, a.min_cov); return -1; }
+    if ((want & WANT_TEXT) && (!a.text || !a.text_bytes)) { mhip_set_error("cns accept: the text was asked for without a place to put it"); return -1; }
+    if ((want & (WANT_PLAN | WANT_READS | WANT_TEXT)) && (a.min_size < 2 || a.min_cov < 1)) { mhip_set_error("cns accept: the plan needs min_size >= 2 and min_cov >= 1 (%d, %d)", a.min_size, a.min_cov); return -1; }
     clear_out(a.accepted); clear_out(a.count); clear_out(a.strings); clear_out(a.strings_bytes); clear_out(a.jobs); clear_out(a.table); clear_out(a.ident); clear_out(a.table_begin);
     clear_out(a.segments); clear_out(a.seg_begin); clear_out(a.windows); clear_out(a.n_windows); clear_out(a.eranges); clear_out(a.erange_begin);
     clear_out(a.pieces); clear_out(a.piece_begin); clear_out(a.cns); clear_out(a.cns_begin);
-    clear_out(a.reads); clear_out(a.read_begin); clear_out(a.seq); clear_out(a.seq_bytes);
+    clear_out(a.reads); clear_out(a.read_begin); clear_out(a.seq); clear_out(a.seq_bytes); clear_out(a.text); clear_out(a.text_bytes);
     return 0;
 }
 
@@ -111,19 +118,20 @@ struct Slice {
 // records are final when they leave the device.  win.bad is CnsPlanDev::d_bad: copied with the windows and looked at in the hand-over
 // only, after every slice has run (an overflow of the segment slots is refused by cns_plan_launch at once).  pc: cns_pieces.hip's slots,
 // cn: cns_poa.hip's bytes, both with begin[] per window of the slice.  rd, sq: cns_reads.hip's records and letters (counts the host knows)
-// with tbegin[nt + 1], the first record of each of the slice's templates [t0, t0 + nt).
-struct PlanSlice { SliceOut seg, win, pc, cn, rd, sq; CnsBuf<int64_t> tbegin; int t0 = 0, nt = 0; };
+// with tbegin[nt + 1], the first record of each of the slice's templates [t0, t0 + nt).  tx: cns_text.hip's bytes (a count the host knows).
+struct PlanSlice { SliceOut seg, win, pc, cn, rd, sq, tx; CnsBuf<int64_t> tbegin; int t0 = 0, nt = 0; };
 
 // the state of one call
 struct Batch {
     const AcceptCall& a;
     mhip_ctx* const c;
-    const bool want_str, want_tab, want_plan, want_pieces, want_poa, want_reads;
+    const bool want_str, want_tab, want_plan, want_pieces, want_poa, want_reads, want_text;
     // build_*: what the outputs asked for read is built on the device either way and copied only when asked for itself — the plan reads the
-    // table, the reads read table, plan and consensus
-    const bool build_plan, build_pieces, build_poa, build_tab;
+    // table, the reads read table, plan and consensus, the text reads the reads
+    const bool build_reads, build_plan, build_pieces, build_poa, build_tab;
     const int threads, start_id, min_run;
     const CnsReplayRules rules;
+    const CnsReplayM4Rules m4;                 // input_type 1
     const double error_rate;                   // mecat_correction.cpp:431 / :494
     double tk[LAP_COUNT] = {}, t_last = now();
     std::vector<int64_t> TB, jfirst;           // per template: first table word (one word per base of every template that has candidates); first job
@@ -151,14 +159,16 @@ struct Batch {
     std::vector<int32_t> ER;
     int64_t seg_total = 0, win_total = 0;
     long long poa_large = 0, poa_chunks = 0;      // windows that went to cns_poa_large, and its launches
-    double reads_wait = 0;                        // host seconds in cns_reads_launch's waits (counted with the plan's as well)
-    int64_t reads_total = 0, seq_total = 0;
+    double reads_wait = 0, text_wait = 0;         // host seconds in cns_reads_launch's and cns_text_launch's waits (counted with the plan's as well)
+    int64_t reads_total = 0, seq_total = 0, text_total = 0;
 
     explicit Batch(const AcceptCall& a_)
         : a(a_), c(a_.c), want_str(a_.want & WANT_STR), want_tab(a_.want & WANT_TAB), want_plan(a_.want & WANT_PLAN), want_pieces(a_.want & WANT_PIECES), want_poa(a_.want & WANT_POA),
-          want_reads(a_.want & WANT_READS), build_plan(want_plan || want_reads), build_pieces(want_pieces || want_poa || want_reads), build_poa(want_poa || want_reads),
+          want_reads(a_.want & WANT_READS), want_text(a_.want & WANT_TEXT), build_reads(want_reads || want_text), build_plan(want_plan || build_reads),
+          build_pieces(want_pieces || want_poa || build_reads), build_poa(want_poa || build_reads),
           build_tab(want_tab || build_plan), threads(std::max(1, a_.num_threads)), start_id(a_.vol->start_read_id), min_run(build_plan ? cns_plan_min_run(a_.min_size) : 0),
-          rules{200, a_.tech == 0 ? 60 : 100, a_.min_mapping_ratio - 0.02}, error_rate(a_.tech == 0 ? 0.15 : 0.20) {}
+          rules{200, a_.tech == 0 ? 60 : 100, a_.min_mapping_ratio - 0.02}, m4{a_.tech == 0 ? 60 : 100, a_.tech != 0, a_.min_mapping_ratio - 0.02},
+          error_rate(a_.tech == 0 ? 0.15 : 0.20) {}
     // no copy may still be writing into a buffer that goes: the body runs before any member is released
     ~Batch() {
         if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
@@ -178,7 +188,8 @@ int sort_and_check(Batch& b) {
         // std::sort, not stable_sort: the reference sorts the same array (file order of the partition) with the same comparator and
         // the same libstdc++ introsort (mecat_correction.cpp:409 / :472), so records that tie on (score, qid, qext) come out in the
         // reference's order exactly when the input order is the reference's — which is what the caller hands over
-        std::sort(s, e, CmpByScore());
+        if (a.input_type == 0) std::sort(s, e, CmpByScore());
+        else cns_replay_m4_order(s, e - s, b.m4);      // (as given, or the whole range by overlap size: the same argument, cns_replay.h)
         for (mhip_ext_candidate* p = s; p < e; ++p) {
             if (p->sdir != 0 || p->qid < start_id || p->qid >= start_id + nreads || p->sid < start_id || p->sid >= start_id + nreads || p->sid != s->sid) { bad = 1; continue; }
             // the record's read lengths are the volume's: the replay indexes the coverage array and the reads with them (the
@@ -191,7 +202,7 @@ int sort_and_check(Batch& b) {
     return 0;
 }
 
-// the first <= 200 candidates of every template, as alignment jobs
+// the first <= 200 candidates (m4 walk: <= max_added overlaps) of every template, as alignment jobs
 void make_jobs(Batch& b) {
     const AcceptCall& a = b.a;
     b.jobs.resize((size_t)b.nj);
@@ -269,7 +280,8 @@ void replay_slice(const Batch& b, Slice& sl) {
     parallel_for(nt, b.threads, [&](int64_t tl) {
         const int64_t t = sl.t0 + tl;
         if (a.tmpl_begin[t + 1] == a.tmpl_begin[t]) return;
-        sl.acc[(size_t)tl] = cns_replay_template(a.cands, a.tmpl_begin, b.res.data(), b.jfirst.data(), t, b.rules);
+        sl.acc[(size_t)tl] = a.input_type == 0 ? cns_replay_template(a.cands, a.tmpl_begin, b.res.data(), b.jfirst.data(), t, b.rules)
+                                               : cns_replay_template_m4(a.cands, a.tmpl_begin, b.res.data(), b.jfirst.data(), t, b.m4);
         if (b.build_plan) {                                         // cns_vec.get_mapping_ranges + get_effective_ranges, :445-447 (tech 1: :509)
             std::vector<std::pair<int32_t, int32_t>> mr;
             for (const int32_t ji : sl.acc[(size_t)tl]) mr.emplace_back(b.res[(size_t)ji].soff, b.res[(size_t)ji].send);
@@ -299,7 +311,7 @@ struct SliceWork {
     int64_t na = 0, tw0 = 0, tw = 0;       // accepted alignments; the slice's table words in the batch's
     size_t a0 = 0;                         // its first accepted record in Avec
     char* d_str = nullptr; uint32_t* d_tab = nullptr; uint8_t* d_id = nullptr;
-    CnsPlanDev pd; CnsPiecesDev qd; CnsPoaDev od; CnsReadsDev rd;
+    CnsPlanDev pd; CnsPiecesDev qd; CnsPoaDev od; CnsReadsDev rd; CnsTextDev td;
     PlanSlice* ps = nullptr;               // with a plan launched
 };
 
@@ -425,7 +437,7 @@ int launch_plan(Batch& b, const Slice& sl, SliceWork& w) {
             if (b.want_poa && !slice_out_alloc(ps.cn, 1, w.od.cap, pd.nwin, b.threads)) { mhip_set_error("out of memory (%lld bytes of consensus)", (long long)w.od.cap); return -1; }
         }
     }
-    if (b.want_reads && pd.nseg > 0) {            // (a segment without a window is a read of its anchors' letters)
+    if (b.build_reads && pd.nseg > 0) {           // (a segment without a window is a read of its anchors' letters)
         std::vector<int32_t> rid((size_t)nt, 0);
         for (int tl = 0; tl < nt; ++tl)
             if (b.a.tmpl_begin[sl.t0 + tl + 1] > b.a.tmpl_begin[sl.t0 + tl]) rid[(size_t)tl] = b.a.cands[b.a.tmpl_begin[sl.t0 + tl]].sid;
@@ -433,10 +445,18 @@ int launch_plan(Batch& b, const Slice& sl, SliceWork& w) {
                              w.od.d_cb, w.od.cap, b.a.min_size, &w.rd)) return -1;
         b.tk[LAP_PLAN_WAIT] += w.rd.wait_s; b.reads_wait += w.rd.wait_s;
         ps.t0 = sl.t0; ps.nt = nt;
-        ps.rd.count = w.rd.nreads; ps.sq.count = w.rd.seq_bytes;
-        ps.tbegin.reset((int64_t*)result_alloc(sizeof(int64_t) * ((size_t)nt + 1), b.threads));
-        if (!slice_out_alloc(ps.rd, sizeof(mhip_cns_read), w.rd.nreads, -1, b.threads) || !slice_out_alloc(ps.sq, 1, w.rd.seq_bytes, -1, b.threads) || !ps.tbegin) {
-            mhip_set_error("out of memory (%lld bytes of corrected reads)", (long long)w.rd.seq_bytes); return -1;
+        if (b.want_reads) {
+            ps.rd.count = w.rd.nreads; ps.sq.count = w.rd.seq_bytes;
+            ps.tbegin.reset((int64_t*)result_alloc(sizeof(int64_t) * ((size_t)nt + 1), b.threads));
+            if (!slice_out_alloc(ps.rd, sizeof(mhip_cns_read), w.rd.nreads, -1, b.threads) || !slice_out_alloc(ps.sq, 1, w.rd.seq_bytes, -1, b.threads) || !ps.tbegin) {
+                mhip_set_error("out of memory (%lld bytes of corrected reads)", (long long)w.rd.seq_bytes); return -1;
+            }
+        }
+        if (b.want_text && w.rd.nreads > 0) {     // behind cns_reads_letters, in front of the copies
+            if (cns_text_launch(c, w.set, w.rd.d_reads, w.rd.nreads, w.rd.d_seq, w.rd.seq_bytes, &w.td)) return -1;
+            b.tk[LAP_PLAN_WAIT] += w.td.wait_s; b.text_wait += w.td.wait_s;
+            ps.tx.count = w.td.bytes;
+            if (!slice_out_alloc(ps.tx, 1, w.td.bytes, -1, b.threads)) { mhip_set_error("out of memory (%lld bytes of text)", (long long)w.td.bytes); return -1; }
         }
     }
     b.seg_total += pd.nseg; b.win_total += pd.nwin;
@@ -474,10 +494,16 @@ int enqueue_copies(Batch& b, const Slice& sl, const SliceWork& w) {
     }
     if (w.rd.d_bad) {                         // (exact sizes: cns_reads_launch has waited for the totals)
         PlanSlice& ps = *w.ps;
-        if (w.rd.nreads) HIPCHK(hipMemcpyAsync(ps.rd.data.get(), w.rd.d_reads, sizeof(mhip_cns_read) * (size_t)w.rd.nreads, hipMemcpyDeviceToHost, cs));
-        if (w.rd.seq_bytes) HIPCHK(hipMemcpyAsync(ps.sq.data.get(), w.rd.d_seq, (size_t)w.rd.seq_bytes, hipMemcpyDeviceToHost, cs));
-        HIPCHK(hipMemcpyAsync(ps.tbegin.get(), w.rd.d_tbegin, sizeof(int64_t) * ((size_t)w.nt + 1), hipMemcpyDeviceToHost, cs));
+        if (b.want_reads) {
+            if (w.rd.nreads) HIPCHK(hipMemcpyAsync(ps.rd.data.get(), w.rd.d_reads, sizeof(mhip_cns_read) * (size_t)w.rd.nreads, hipMemcpyDeviceToHost, cs));
+            if (w.rd.seq_bytes) HIPCHK(hipMemcpyAsync(ps.sq.data.get(), w.rd.d_seq, (size_t)w.rd.seq_bytes, hipMemcpyDeviceToHost, cs));
+            HIPCHK(hipMemcpyAsync(ps.tbegin.get(), w.rd.d_tbegin, sizeof(int64_t) * ((size_t)w.nt + 1), hipMemcpyDeviceToHost, cs));
+        }
         HIPCHK(hipMemcpyAsync(&ps.rd.bad, w.rd.d_bad, sizeof(long long), hipMemcpyDeviceToHost, cs));
+    }
+    if (w.td.d_bad) {                         // (exact size: cns_text_launch has waited for the total)
+        HIPCHK(hipMemcpyAsync(w.ps->tx.data.get(), w.td.d_text, (size_t)w.td.bytes, hipMemcpyDeviceToHost, cs));
+        HIPCHK(hipMemcpyAsync(&w.ps->tx.bad, w.td.d_bad, sizeof(long long), hipMemcpyDeviceToHost, cs));
     }
     if (w.tw && b.want_tab) {
         HIPCHK(hipMemcpyAsync(b.tab.get() + w.tw0, w.d_tab, sizeof(uint32_t) * (size_t)w.tw, hipMemcpyDeviceToHost, cs));
@@ -511,7 +537,7 @@ template <typename T> CnsBuf<T> copy_of(const T* src, size_t n) {
     return p;
 }
 
-struct PlanResult { CnsBuf<void> seg, win, pc, cn, reads, seq; CnsBuf<int64_t> seg_begin, erange_begin, piece_begin, cns_begin, read_begin; CnsBuf<int32_t> eranges; };
+struct PlanResult { CnsBuf<void> seg, win, pc, cn, reads, seq, text; CnsBuf<int64_t> seg_begin, erange_begin, piece_begin, cns_begin, read_begin; CnsBuf<int32_t> eranges; };
 
 // concat_slices over one member of the plan's slices; its refusals in the output's own words (counts: two %lld, no_memory: one)
 struct ConcatTexts { const char *bad, *counts, *no_memory; };
@@ -579,6 +605,13 @@ int put_plan_together(Batch& b, PlanResult& r) {
     if (b.want_poa && concat(b, &PlanSlice::cn, 1, &r.cn, &r.cns_begin, {poa_bad,
                                                                           "cns poa: inconsistent counts (%lld bytes in %lld)", "out of memory (%lld bytes of consensus)"})) return -1;
     if (b.want_reads && put_reads_together(b, r)) return -1;
+    if (b.want_text) {                         // (template order, whole templates per slice: the slices' texts as they are, one behind the other)
+        for (const PlanSlice& p : b.plan)
+            if (p.rd.bad) { mhip_set_error("cns reads: an index left its array, or the letters written are not the letters counted"); return -1; }
+        if (concat(b, &PlanSlice::tx, 1, &r.text, nullptr, {"cns text: a record leaves the letters or holds a negative number, or the bytes written are not the bytes counted", "",
+                                                             "out of memory (%lld bytes of text)"})) return -1;
+        for (const PlanSlice& p : b.plan) b.text_total += p.tx.count;
+    }
     if (!b.want_plan) return 0;
     for (size_t t = 0; t + 1 < n1; ++t) b.ERB[t + 1] += b.ERB[t];          // counts -> first range of every template
     r.seg_begin = copy_of(b.SB.data(), n1); r.erange_begin = copy_of(b.ERB.data(), n1); r.eranges = copy_of(b.ER.data(), b.ER.size());
@@ -610,6 +643,8 @@ int hand_over(Batch& b) {
         if (b.want_reads)
             fprintf(stderr, "[cns_accept] reads: %lld records, %lld bytes of corrected reads: waited for the totals %.3f s (counted with the plan's waits)\n", (long long)b.reads_total,
                     (long long)b.seq_total, b.reads_wait);
+        if (b.want_text)
+            fprintf(stderr, "[cns_accept] text: %lld bytes: waited for the totals %.3f s (counted with the plan's waits)\n", (long long)b.text_total, b.text_wait);
         if (b.build_plan)
             fprintf(stderr, "[cns_accept] plan: %lld segments, %lld windows: waited for the counts %.3f s (within strings launched), slices' pieces put together %.3f (within last copies)\n",
                     (long long)b.seg_total, (long long)b.win_total, tk[LAP_PLAN_WAIT], tk[LAP_PUT]);
@@ -623,6 +658,7 @@ int hand_over(Batch& b) {
     if (b.want_pieces) { *a.pieces = (mhip_cns_piece*)r.pc.release(); *a.piece_begin = r.piece_begin.release(); }
     if (b.want_poa) { *a.cns = (char*)r.cn.release(); *a.cns_begin = r.cns_begin.release(); }
     if (b.want_reads) { *a.reads = (mhip_cns_read*)r.reads.release(); *a.read_begin = r.read_begin.release(); *a.seq = (char*)r.seq.release(); *a.seq_bytes = b.seq_total; }
+    if (b.want_text) { *a.text = (char*)r.text.release(); *a.text_bytes = b.text_total; }
     return 0;
 }
 
@@ -641,7 +677,8 @@ int run(const AcceptCall& a, int allowed) {
     if (b.build_plan) { b.SB.assign((size_t)T + 1, 0); b.ERB.assign((size_t)T + 1, 0); }
     b.lap(LAP_SORT);
     b.jfirst.assign((size_t)T + 1, 0);
-    for (int t = 0; t < T; ++t) b.jfirst[(size_t)t + 1] = b.jfirst[(size_t)t] + std::min<int64_t>(b.rules.max_ext, a.tmpl_begin[t + 1] - a.tmpl_begin[t]);
+    const int64_t max_jobs = a.input_type == 0 ? b.rules.max_ext : b.m4.max_added;
+    for (int t = 0; t < T; ++t) b.jfirst[(size_t)t + 1] = b.jfirst[(size_t)t] + std::min<int64_t>(max_jobs, a.tmpl_begin[t + 1] - a.tmpl_begin[t]);
     b.nj = b.jfirst[(size_t)T];
     if (a.jobs) *a.jobs = b.nj;
     if (b.nj == 0) return hand_over(b);
@@ -723,6 +760,26 @@ int mhip_cns_accept_templates_reads(mhip_ctx* c, const mhip_volume* vol, mhip_ex
     return run({c, vol, cands, tmpl_begin, num_templates, tech, min_align_size, min_mapping_ratio, num_threads, want, min_cov, min_size, out_accepted, out_count, out_strings, out_strings_bytes,
                 out_jobs, out_table, out_ident, out_table_begin, out_segments, out_seg_begin, out_windows, out_n_windows, out_eranges, out_erange_begin, out_pieces, out_piece_begin, out_cns,
                 out_cns_begin, out_reads, out_read_begin, out_seq, out_seq_bytes}, WANT_STR | WANT_TAB | WANT_PLAN | WANT_PIECES | WANT_POA | WANT_READS);
+}
+
+int mhip_cns_correct_templates(mhip_ctx* c, const mhip_volume* vol, mhip_ext_candidate* cands, const int64_t* tmpl_begin, int num_templates, const mhip_cns_opts* o,
+                               mhip_cns_outputs* out) {
+    if (!o || !out) { mhip_set_error("cns accept: the options or the outputs are NULL"); return -1; }
+    *out = mhip_cns_outputs();
+    AcceptCall a{c, vol, cands, tmpl_begin, num_templates, o->tech, o->min_align_size, o->min_mapping_ratio, o->num_threads, o->want, o->min_cov, o->min_size,
+                 &out->accepted, &out->count, &out->strings, &out->strings_bytes, &out->jobs, &out->table, &out->ident, &out->table_begin, &out->segments, &out->seg_begin,
+                 &out->windows, &out->n_windows, &out->eranges, &out->erange_begin, &out->pieces, &out->piece_begin, &out->cns, &out->cns_begin, &out->reads, &out->read_begin,
+                 &out->seq, &out->seq_bytes};
+    a.input_type = o->input_type; a.text = &out->text; a.text_bytes = &out->text_bytes;
+    return run(a, WANT_STR | WANT_TAB | WANT_PLAN | WANT_PIECES | WANT_POA | WANT_READS | WANT_TEXT);
+}
+
+void mhip_cns_outputs_free(mhip_cns_outputs* out) {
+    if (!out) return;
+    void* const p[] = {out->accepted, out->strings, out->table, out->ident, out->table_begin, out->segments, out->seg_begin, out->windows, out->eranges, out->erange_begin,
+                       out->pieces, out->piece_begin, out->cns, out->cns_begin, out->reads, out->read_begin, out->seq, out->text};
+    for (void* x : p) if (x) mhip_cns_free(x);
+    *out = mhip_cns_outputs();
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 
 #include "cns_poa.h"
 #include "cns_reads.h"
+#include "cns_text.h"
 
 namespace {
 
@@ -48,6 +49,12 @@ void cns_reads_host_block(int64_t size, int64_t k, int64_t beg, int64_t end, int
     cns_reads_block(size, k, beg, end, &L, &R, &rb, &re);
     out[0] = L; out[1] = R; out[2] = rb; out[3] = re;
 }
+
+// the corrected reads' text rule (cns_text.h), the code cns_text_write runs: characters of a record's header line and of the whole record,
+// and character l of the header line (0 behind its newline)
+int cns_text_host_header_len(int32_t read_id, int32_t range_beg, int32_t range_end, int32_t size) { return cns_text_header_len(read_id, range_beg, range_end, size); }
+int64_t cns_text_host_record_len(int32_t read_id, int32_t range_beg, int32_t range_end, int32_t size) { return cns_text_record_len(read_id, range_beg, range_end, size); }
+int cns_text_host_header_char(int32_t read_id, int32_t range_beg, int32_t range_end, int32_t size, int l) { return cns_text_header_char(read_id, range_beg, range_end, size, l); }
 
 // One template: n_alns alignments (alignment a: qaln at buf + off[a], len[a] characters + NUL, saln right behind it), n_windows windows
 // as triples (sb, se, cov), their pieces as records (aln, col, ncols, sb_out), window w owning [piece_begin[w], piece_begin[w + 1]).

@@ -226,7 +226,7 @@ int cns_reads_launch(mhip_ctx* c, int set, const uint32_t* d_table, const uint8_
     if (tot[0] < 0 || tot[1] < 0 || tot[1] > tot[0]) { mhip_set_error("cns reads: inconsistent totals (%lld letters, %lld records)", tot[0], tot[1]); return -1; }
     char* d_seq;
     mhip_cns_read* d_reads;
-    if (buf("cr_seq", (size_t)tot[0], (void**)&d_seq)) return -1;
+    if (buf("cr_seq", (size_t)tot[0] + 16, (void**)&d_seq)) return -1;      // (+ 16: cns_text_write reads whole aligned 16-byte words)
     if (buf("cr_reads", sizeof(mhip_cns_read) * (size_t)tot[1], (void**)&d_reads)) return -1;
     const unsigned grid_r = (unsigned)std::max<long long>(1, std::min<long long>((nseg + nt + 1 + 255) / 256, (long long)max_grid * 4));
     LAUNCH(c, "cns_reads_records", cns_reads_records, grid_r, 256, 0, d_seg, nseg, d_segb, seg_base, nt, t_index0, d_rid, d_tlen, d_sbeg, d_rbeg, tot[1], tot[0], d_reads, d_tbegin,

@@ -54,6 +54,19 @@ assert CAND_DTYPE.itemsize == C.sizeof(Candidate) == 48
 _lib = None
 
 
+class CnsOpts(C.Structure):      # mhip_cns_opts
+    _fields_ = [(n, C.c_int) for n in ("tech", "input_type", "min_align_size", "min_cov", "min_size", "num_threads", "want")] + [("min_mapping_ratio", C.c_double)]
+
+
+class CnsOutputs(C.Structure):      # mhip_cns_outputs
+    _fields_ = [("accepted", C.c_void_p), ("count", C.c_int64), ("strings", C.c_void_p), ("strings_bytes", C.c_int64), ("jobs", C.c_int64),
+                ("table", C.c_void_p), ("ident", C.c_void_p), ("table_begin", C.c_void_p),
+                ("segments", C.c_void_p), ("seg_begin", C.c_void_p), ("windows", C.c_void_p), ("n_windows", C.c_int64),
+                ("eranges", C.c_void_p), ("erange_begin", C.c_void_p), ("pieces", C.c_void_p), ("piece_begin", C.c_void_p),
+                ("cns", C.c_void_p), ("cns_begin", C.c_void_p), ("reads", C.c_void_p), ("read_begin", C.c_void_p), ("seq", C.c_void_p),
+                ("seq_bytes", C.c_int64), ("text", C.c_void_p), ("text_bytes", C.c_int64)]
+
+
 def lib():
     """Loads libmecat_hip.so; raises (never falls back) when it is missing."""
     global _lib
@@ -137,6 +150,10 @@ def lib():
     L.mhip_cns_format_reads.argtypes = [vp, i64, vp, i64, pvp, pi64]
     L.mhip_debug_cns_reads.argtypes = [vp, vp, vp, vp, i32, vp, vp, i64, vp, i64, vp, vp, i32, pvp, pvp, pvp, pi64]
     L.mhip_debug_cns_correct.argtypes = [vp, vp, i64, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, pvp, pi64, pvp, pi64]
+    L.mhip_cns_correct_templates.argtypes = [vp, vp, vp, vp, i32, C.POINTER(CnsOpts), C.POINTER(CnsOutputs)]
+    L.mhip_cns_outputs_free.argtypes = [C.POINTER(CnsOutputs)]
+    L.mhip_cns_outputs_free.restype = None
+    L.mhip_debug_cns_text.argtypes = [vp, vp, i64, vp, i64, pvp, pi64]
     L.mhip_cns_poa_small_words.restype = i64
     L.mhip_cns_poa_small_words.argtypes = []
     L.mhip_cns_free.argtypes = [vp]
@@ -576,7 +593,7 @@ def cns_accept_templates_plan(ctx, vol, cands, tmpl_begin, tech, min_align_size,
     """cns_accept_templates_ex with CNS_WANT_PLAN allowed in `want`: the consensus plan of every template, computed on the device behind
     its table — effective ranges (get_effective_ranges), the segments consensus_worker would correct (runs of mat_cnt + ins_cnt >= min_cov
     of at least 0.95 * min_size positions inside an effective range) and per segment the windows meap_consensus_one_segment hands to the
-    POA (anchor to next anchor, some position in between UNDS or FDEL).  The mecat2cns defaults: min_cov 4 / min_size 5000 (PacBio),
+    POA (anchor to next anchor, some position in between UNDS or FDEL).  The mecat2cns defaults: min_cov 6 / min_size 5000 (PacBio),
     6 / 2000 (nanopore).  -> cns_accept_templates_ex's tuple + a dict: segments [SEGMENT_DTYPE] in template order then ascending beg,
     seg_begin [templates + 1], windows [WINDOW_DTYPE] in segment order then ascending sb (segment s owns windows[win_begin: win_end]),
     eranges [k, 2], erange_begin [templates + 1]; None without CNS_WANT_PLAN.  With CNS_WANT_PLAN alone neither strings nor tables are
@@ -699,6 +716,63 @@ def cns_format_reads(reads, seq):
     seq = np.ascontiguousarray(seq, dtype=np.uint8)
     text, n = C.c_void_p(), C.c_int64()
     _chk(lib().mhip_cns_format_reads(reads.ctypes.data, len(reads), seq.ctypes.data, len(seq), C.byref(text), C.byref(n)))
+    return _cns_take(text, np.uint8, n.value).tobytes()
+
+
+CNS_WANT_TEXT = 64
+
+
+def cns_correct_templates(ctx, vol, cands, tmpl_begin, tech, min_align_size, min_mapping_ratio, want, min_cov, min_size, input_type=0, threads=8):
+    """mhip_cns_correct_templates: cns_accept_templates_reads with the options and outputs in structs, CNS_WANT_TEXT allowed in `want`
+    (the reference's FASTA text of the records, made on the device; alone it copies the accepted records and the text, nothing else) and
+    input_type 1 for the m4 walk (a template's records are overlaps in the order given; see mecat_hip.h).  -> (the tuple of
+    cns_accept_templates_reads, the text as bytes or None without the bit, cands as the call left them, and per pointer member of the
+    outputs whether it came back NULL)"""
+    cands = np.array(cands, copy=True)
+    tb = np.ascontiguousarray(tmpl_begin, dtype=np.int64)
+    want = int(want)
+    nt = len(tb) - 1
+    o = CnsOpts(int(tech), int(input_type), int(min_align_size), int(min_cov), int(min_size), int(threads), want, float(min_mapping_ratio))
+    r = CnsOutputs()
+    _chk(lib().mhip_cns_correct_templates(ctx.h, vol.h, cands.ctypes.data, tb.ctypes.data, nt, C.byref(o), C.byref(r)))
+    null = {k: getattr(r, k) is None for k, t in CnsOutputs._fields_ if t is C.c_void_p}
+    def take(name, dtype, n):      # a copy of the member's records; the member is released and cleared
+        x = _cns_take(C.c_void_p(getattr(r, name)), dtype, n)
+        setattr(r, name, None)
+        return x
+    a = take("accepted", ACCEPTED_DTYPE, r.count)
+    s = take("strings", np.uint8, r.strings_bytes)
+    begin = take("table_begin", np.int64, nt + 1)
+    nw = int(begin[-1]) if len(begin) else 0
+    tab, idn = take("table", np.uint8, 4 * nw).view(TABLE_DTYPE), take("ident", np.uint8, nw)
+    plan = None
+    if want & CNS_WANT_PLAN:
+        segb, erb = take("seg_begin", np.int64, nt + 1), take("erange_begin", np.int64, nt + 1)
+        plan = dict(segments=take("segments", SEGMENT_DTYPE, int(segb[-1]) if len(segb) else 0), seg_begin=segb,
+                    windows=take("windows", WINDOW_DTYPE, int(r.n_windows)),
+                    eranges=take("eranges", np.int32, 2 * (int(erb[-1]) if len(erb) else 0)).reshape(-1, 2), erange_begin=erb)
+        if want & CNS_WANT_PIECES:
+            plan["piece_begin"] = take("piece_begin", np.int64, int(r.n_windows) + 1)
+            plan["pieces"] = take("pieces", PIECE_DTYPE, int(plan["piece_begin"][-1]) if len(plan["piece_begin"]) else 0)
+        if want & CNS_WANT_POA:
+            plan["cns_begin"] = take("cns_begin", np.int64, int(r.n_windows) + 1)
+            plan["cns"] = take("cns", np.uint8, int(plan["cns_begin"][-1]) if len(plan["cns_begin"]) else 0)
+    rd = None
+    if want & CNS_WANT_READS:
+        rb = take("read_begin", np.int64, nt + 1)
+        rd = dict(reads=take("reads", READ_DTYPE, int(rb[-1]) if len(rb) else 0), read_begin=rb, seq=take("seq", np.uint8, r.seq_bytes))
+    text = take("text", np.uint8, r.text_bytes).tobytes() if want & CNS_WANT_TEXT else None
+    jobs = r.jobs
+    lib().mhip_cns_outputs_free(C.byref(r))      # (whatever the wanted bits did not take)
+    return (a, s, jobs, tab, idn, begin, plan, rd), text, cands, null
+
+
+def debug_cns_text(ctx, reads, seq):
+    """test hook: the text kernels alone on host-supplied records (see mecat_hip.h) -> bytes"""
+    reads = np.ascontiguousarray(reads, dtype=READ_DTYPE)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    text, n = C.c_void_p(), C.c_int64()
+    _chk(lib().mhip_debug_cns_text(ctx.h, reads.ctypes.data, len(reads), seq.ctypes.data, len(seq), C.byref(text), C.byref(n)))
     return _cns_take(text, np.uint8, n.value).tobytes()
 
 

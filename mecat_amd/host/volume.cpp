@@ -508,6 +508,36 @@ int split_raw_dataset(const char* reads, const char* wrk_dir, int num_threads) {
     return vol;
 }
 
+int load_reads_in_memory(const char* reads, long max_read_size, HostVolume* v, long* bad_read) {
+    *v = HostVolume();
+    LineReader lr(reads);
+    std::string seq;
+    long curr = 0;
+    while (true) {
+        bool have_header;
+        const long rsize = read_one_seq(lr, seq, &have_header);
+        if (rsize == -1) break;
+        if (rsize >= max_read_size) { *bad_read = (long)v->offs.size(); return 1; }
+        if (curr + rsize + 1 > kMaxVolumeBases) return 2;
+        mhip_offset_t o;
+        o.offset = (int)curr;
+        o.size = (int)rsize;
+        v->offs.push_back(o);
+        const size_t need = ((size_t)(curr + rsize + 1) + 3) / 4;
+        if (v->pac.size() < need) v->pac.resize(std::max(need, v->pac.size() * 2), 0);
+        for (long i = 0; i < rsize; ++i, ++curr) {
+            const uint8_t c = kEnc.t[(unsigned char)seq[(size_t)i]];
+            v->pac[(size_t)(curr >> 2)] |= (uint8_t)((c < 4 ? c : 0) << ((~curr & 3) << 1));
+        }
+        ++curr;   // pad base
+    }
+    v->num_bases = (int)curr;
+    v->num_reads = (int)v->offs.size();
+    v->start_read_id = 0;
+    v->pac.resize(((size_t)curr + 3) / 4, 0);
+    return 0;
+}
+
 bool volume_dump_in_flight() { return g_pending.joinable(); }
 void volume_set_device_packer(std::function<mhip_ctx*()> get_ctx) { g_device_ctx = std::move(get_ctx); }
 

@@ -67,3 +67,8 @@ bool volume_dump_in_flight();      // the second thread may still be writing a v
 // goes with the process.
 void volume_release_input();
 void load_volume(const std::string& path, HostVolume* v);        // split_database.cpp:155-181 (exit(1) if missing)
+// The whole FASTA / FASTQ as ONE volume in memory, through the same reader (grammar and error messages of FastaReader): no vol<k> file,
+// no working directory.  Read ids are file order from 0, as PackedDB::load_fasta_db assigns them (mecat2cns).  Letters other than
+// A, C, G and T are stored as A (the reference's PackedDB draws rand() & 3 for them, packed_db.cpp:158).
+// Returns 0; 1 when read *bad_read has max_read_size letters or more; 2 when the reads do not fit one volume (num_bases is an int).
+int load_reads_in_memory(const char* reads, long max_read_size, HostVolume* v, long* bad_read);
