@@ -19,10 +19,13 @@
 // have loop bodies of their own.  Inside a block the row code keeps positions in doubled units (2 x is its own v_alignbit shift operand),
 // counts the rows of the two fast loops on the scalar unit, and takes the band update's first diagonal and slot count from the scalar
 // unit as one packed word per half (profiles/dw_row_trims.md); the code around the row loops works in base units.
-// 64 VGPRs, 19 KB of LDS per four waves, eight waves per SIMD (tests/test_dw_resources_cpu.py holds the compiler to it); a one-pass
-// dual row is 48 VALU (146 issue cycles) + 27 SALU, a two-pass row 81 (248) + 48 (tests/test_dw_row_cycles_cpu.py caps the cycles);
-// VALU-issue bound (profiles/r03_dw_row_breakdown.md, r05_dw_attempt.md).  The code between two row loops is 10 % of a wave's life
-// (profiles/dw_block_setup.md).  What is and is not settled about the row loops: DESIGN.md §6.
+// A snake step makes one compare, nn == what is left of the window, and looks closer only when an active lane has it (snake_step_end);
+// idle lanes are not parked, every consumer masks them (profiles/dw_snake_compare.md).
+// 64 VGPRs, 19 KB of LDS per four waves, eight waves per SIMD (tests/test_dw_resources_cpu.py holds the compiler to it); on its common
+// path a one-pass dual row is 46 VALU (138 issue cycles) + 25 SALU, a two-pass row 77 (232) + 46 (tests/test_dw_row_cycles_cpu.py caps
+// the cycles, counting the rare part of the snake step too: 142 / 240); VALU-issue bound (profiles/r03_dw_row_breakdown.md,
+// r05_dw_attempt.md).  The code between two row loops is 10 % of a wave's life (profiles/dw_block_setup.md).  What is and is not
+// settled about the row loops: DESIGN.md §6.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -94,6 +97,40 @@ template <int OFF> __device__ __forceinline__ unsigned long long clamped_bits_at
     int c;
     asm("s_min_i32 %1, %2, 32\n\ts_max_i32 %1, %1, 0\n\ts_bfm_b64 %0, %1, %3" : "=s"(r), "=&s"(c) : "s"(n), "n"(OFF) : "scc");
     return r;
+}
+
+// The end of a snake step of dw_extend2 (see row_passes).  at_lim: the lanes with nn == limc, i.e. whose window (limc == 32 == nn) or block
+// (limc < 32) ran out in this step; amask: the pass's active lanes.  Returns the active lanes that want another step (nn == 32).  No
+// active lane in at_lim — 97 % of the passes — is one s_and_b64 and a branch.  Otherwise, once no lane goes on, the active lanes of
+// at_lim are the diagonals that reached an end of the block (a lane that ended in an earlier step has limc == 0 == nn in the later ones):
+// they are added to `ended`, and the row loops' count-down (rows_more >= 0 here) gets its two top bits set, which takes the row loop out
+// through its bound (ROWS_ENDED; rows_more_value() gives the count back).
+// One asm statement with a forward branch inside: written as an `if` in the snake loop, the rare part gives the loop a second exit or a
+// block between its header and its latch, and the compiler (loop-exit unification, CFG structurisation: they run on uniform branches
+// too) then carries flag registers, their moves and a second re-tested branch around every step (profiles/dw_snake_compare.md).
+#define ROWS_ENDED 0xc0000000u
+__device__ __forceinline__ unsigned long long snake_step_end(unsigned long long at_lim, unsigned long long amask, int nn,
+                                                             unsigned long long& ended, int& rows_more) {
+    unsigned long long more;
+    int mark;
+    asm("s_and_b64 %[more], %[at], %[am]\n\t"
+        "s_cbranch_scc0 1f\n\t"
+        "v_cmp_eq_u32 vcc, 32, %[nn]\n\t"
+        "s_and_b64 vcc, vcc, %[more]\n\t"             // the lanes that go on; SCC: there are some
+        "s_cselect_b64 %[more], 0, %[more]\n\t"       // the lanes that ended, once nobody goes on
+        "s_cselect_b32 %[mark], 0, 0xc0000000\n\t"
+        "s_or_b32 %[rm], %[rm], %[mark]\n\t"
+        "s_or_b64 %[en], %[en], %[more]\n\t"
+        "s_mov_b64 %[more], vcc\n"
+        "1:"
+        : [more] "=&s"(more), [mark] "=&s"(mark), [en] "+s"(ended), [rm] "+s"(rows_more)
+        : [at] "s"(at_lim), [am] "s"(amask), [nn] "v"(nn)
+        : "vcc", "scc");
+    return more;
+}
+// the count-down behind a row: what it would be had snake_step_end not marked it (the caller has taken the row off: - 1)
+__device__ __forceinline__ int rows_more_value(int rows_more, bool marked) {
+    return marked ? (int)(((unsigned)rows_more + 1u) & ~ROWS_ENDED) - 1 : rows_more;
 }
 
 #ifndef DW2_WAVES_PER_SIMD
@@ -228,7 +265,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 // a live diagonal has x <= q_len and its window is words x >> 4 and (x >> 4) + 1, so every base it sees at or beyond
                 // q_len (t_len for the target) sits at window offset >= lim = min(q_len - x, t_len - y).  A first difference in
                 // front of lim lies inside the valid bases of both sequences, and anything at or behind lim is clamped away by
-                // v_min3_i32(m, lim, 16); the end test lim == nn is decided by the same two cases.  Idle lanes keep nothing.
+                // min(m, min3(q_len - x, t_len - y, 16)); the end test nn == limc is decided by the same two cases.  Idle lanes keep nothing.
                 // Words 32 .. are staged only when a half in set-up has a block of more than 512 bases (a last block; the test is
                 // wave-uniform): a full block stages in one trip.
                 static_assert((SEG_BLK + 99) * 6 / 5 <= 16 * (SEQ_WORDS2 - 1), "the longest block and one 16-base window fit the staged words");
@@ -378,14 +415,14 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
         // last lane: the caller's business, see `full` below).  What idle lanes write beyond it is overwritten by the rows that
         // follow, except for up to 64 entries behind the last row of a block with NJ <= 2: the tail traceback's window is shortened
         // by as much (rows with more passes guard their stores).  FAST 1: 1 <= slots <= 32 in both halves, one pass; FAST 2: 1 <= slots
-        // <= 63, two passes; FAST 0: anything.
-        auto row_passes = [&](const int NJ, const int ns_a, const int ns_b, auto fast_tag) __attribute__((always_inline)) {
+        // <= 63, two passes; FAST 0: anything.  rows_more: the caller's count-down of rows, which a pass marks — and `ended` gets the
+        // lanes — when a diagonal reached an end of its block (snake_step_end).
+        auto row_passes = [&](const int NJ, const int ns_a, const int ns_b, int& rows_more, auto fast_tag) __attribute__((always_inline)) {
             constexpr int FAST = decltype(fast_tag)::value;
 
             row_bytes = twice((unsigned)nslot) + 2u;
             last_ns = nslot;
             int mmax = -0x40000000, m0 = -0x40000000, mp = -0x40000000;
-            unsigned long long e = 0;
             int j = 0;
             do {                                 // at least one pass (a pass over an empty band only moves idle lanes)
                 const int tt = sl + 32 * j;
@@ -411,7 +448,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 // <= 2 vr - (k + 1) in base units, i.e. vl + 1 < vr; mirrored at k == max_k (vr is negative, or a dropped diagonal with
                 // vr < vl + 1).  So the two edge tests fold into the same max — in the 16-bit forms of add and max, which issue at twice the
                 // rate of the 32-bit max (the result is >= 0 and comes back zero-extended).
-                int x;                           // x2 (and y, lim, nn, m0 below: y2, 2 lim, 2 nn, 2 (x + y))
+                int x;                           // x2 (and y, limc, nn, m0 below: y2, 2 limc, 2 nn, 2 (x + y))
                 {
                     int v1;
                     asm("v_add_u16 %0, 2, %1" : "=v"(v1) : "v"(vl));
@@ -430,36 +467,39 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                         fl2 = j == 2 ? fb : fl2;
                     }
                 }
-                // 0 <= y <= t_len and x <= q_len on every live diagonal (a diagonal at an end stops the block); idle lanes sit
-                // at (q_len, 0), where lim == 0
-                x = act ? x : q_len2;
-                // (idle lanes: lim <= 0 whatever y is, so they never move forward and never ask for another step; their window
-                // loads may fall outside the staged block or outside the LDS allocation, where reads return 0: nothing of an
-                // idle lane is kept — the stored value, the end mask and m0 below are all guarded by `act`)
+                // 0 <= y <= t_len and x <= q_len on every live diagonal (a diagonal at an end stops the block).
+                // Idle lanes are not parked: they start from whatever max(vl + 2, vr) of the ring gives them (0 .. 65535) and snake on it.
+                // All they do is load — window words from anywhere in or beyond the LDS allocation, where reads return 0 — and nothing
+                // of theirs is kept, each consumer guarding itself: the stored value is `act ? x : sepv` (FAST 0: under tt <= nslot), m0 is
+                // `act ? x + y : -inf` (so neither the row maximum nor the band update sees them), snake_step_end masks the lanes at
+                // their limit with amask — an idle lane neither asks for a further step nor ends a block —, and the CNS flag bits are
+                // masked by the reader with the row's slot count.  Nothing behind the passes reads a lane's x, y, limc or nn.
                 int y = x - k2;
-                int lim, nn;
 #ifdef MECAT_DW_STATS
                 snake2 -= 1;
 #endif
+                unsigned long long more;
                 do {
 #ifdef MECAT_DW_STATS
                     snake2 += 1;
 #endif
-                    lim = min(q_len2 - x, t_len2 - y);
+                    // what is left of the window: of the query, of the target, 16 bases
+                    int limc;
+                    asm("v_min3_i32 %0, %1, %2, 32" : "=v"(limc) : "v"(q_len2 - x), "v"(t_len2 - y));
                     // 0..15 equal bases (doubled: 0..30), or >= 16 (0x7ffffffe) when the whole window matches.  A lane with exactly 16
                     // bases left that all match asks for one more step, which then moves nothing.
                     const int m = match16_le2(S.Qp, x, S.Tp, y);
-                    asm("v_min3_i32 %0, %1, %2, 32" : "=v"(nn) : "v"(m), "v"(lim));
+                    const int nn = min(m, limc);
+                    // one compare per step: nn == limc holds exactly on the lanes that go on (limc == 32) or have nothing left of the
+                    // query or of the target on their diagonal (limc < 32); which of the two is looked at only when an active lane has it
                     x += nn; y += nn;
-                } while (BALLOT(nn == 32));
+                    more = snake_step_end(BALLOT(nn == limc), amask, nn, ended, rows_more);
+                } while (more);
                 if (NJ <= 2 || tt <= nslot) ring_st(rbase, lin_l + 64u * (unsigned)j, act ? x : sepv);
-                // nothing left of the query or of the target on this diagonal
-                e |= BALLOT(lim == nn) & amask;
                 mp = m0;
                 m0 = act ? x + y : -0x40000000;     // also read by the band update (NJ <= 2); idle lanes never qualify
                 mmax = NJ == 1 ? m0 : max(mmax, m0);
             } while (++j < NJ);
-            ended = e;
             last_m0 = m0; last_mp = mp;
             rlin_l = lin_l;                      // (the caller moves lin_l behind the row and the entry behind it: lin_l += row_bytes)
             __builtin_amdgcn_wave_barrier();
@@ -508,7 +548,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
             // its per-half values without the `inblock` guard, and the loop control is scalar — the rows the two blocks may still run
             // (d < dlim in both) as one count-down, the band-size limits (:118 "max_k - min_k <= band_size") of the two halves next to
             // the slot counts, which are on the scalar unit anyway.  One-pass rows run in a loop of their own.
-            int rows_left = min(__builtin_amdgcn_readlane(dlim - d, 0), __builtin_amdgcn_readlane(dlim - d, 32));
+            const int rows_left = min(__builtin_amdgcn_readlane(dlim - d, 0), __builtin_amdgcn_readlane(dlim - d, 32));
             const int lim_a = (__builtin_amdgcn_readlane(band_tol2, 0) >> 1) + 1, lim_b = (__builtin_amdgcn_readlane(band_tol2, 32) >> 1) + 1;
             const int one_a = min(lim_a, 32), one_b = min(lim_b, 32);
             const int two_a = min(lim_a, 63), two_b = min(lim_b, 63);
@@ -516,49 +556,45 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
             typedef std::integral_constant<int, 1> fast1;
             typedef std::integral_constant<int, 2> fast2;
             // Both halves advance by the same rows here and nothing in the loops reads d: the rows are counted on the scalar unit and
-            // added to d once behind the loops (a per-lane d += go is a v_addc per row).
-            int rows_run = 0;
+            // added to d once behind the loops (a per-lane d += go is a v_addc per row).  One counter does it: rows_more, the rows that
+            // may run behind the current one, which is also the loops' bound; a row that reached an end marks it (snake_step_end).
+            int rows_more = rows_left - 1;
             while (true) {
                 // one-pass rows (rows left, and both slot counts within their limits: one sign test)
-                while (((rows_left - 1) | (one_a - ns_a) | (one_b - ns_b)) >= 0) {
+                while ((rows_more | (one_a - ns_a) | (one_b - ns_b)) >= 0) {
                     DWS_ROW(~0ull, ns_a, ns_b, 1);
-                    rows_left -= 1;
-                    rows_run += 1;
                     const bool full = ((ns_a | ns_b) & 32) != 0;       // a half has all of its 32 lanes on diagonals: nobody stores the entry
-                    row_passes(1, ns_a, ns_b, fast1{});                //   behind its row (the other half's idle lane rewrites its own)
+                    row_passes(1, ns_a, ns_b, rows_more, fast1{});     //   behind its row (the other half's idle lane rewrites its own)
                     lin_l += row_bytes;
                     if (full) ring_st(rbase, lin_l - 2u * sl - 2u, sepv);
                     band_update(1, last_m0, last_mp, std::true_type{}, ns_a, ns_b);
                     log_row(1, std::true_type{});
-                    // (a row that reached an end leaves the loop through its bound: a second exit makes the compiler build a machine of
-                    // flag registers and re-tested branches around every row)
-                    rows_left = ended ? -1 : rows_left;
+                    // (a row that reached an end leaves the loop through its bound, which snake_step_end has marked: a second exit makes
+                    // the compiler build a machine of flag registers and re-tested branches around every row)
+                    rows_more -= 1;
                     __builtin_amdgcn_wave_barrier();
                 }
                 if (ended) break;
                 // two-pass rows: a half has 33 .. 63 slots
-                while (((rows_left - 1) | (two_a - ns_a) | (two_b - ns_b) | (max(ns_a, ns_b) - 33)) >= 0) {      // (one sign test: rows left, slot counts within 33 .. limit)
+                while ((rows_more | (two_a - ns_a) | (two_b - ns_b) | (max(ns_a, ns_b) - 33)) >= 0) {      // (one sign test: rows left, slot counts within 33 .. limit)
                     DWS_ROW(~0ull, ns_a, ns_b, 2);
                     NJ = 2;
-                    rows_left -= 1;
-                    rows_run += 1;
-                    row_passes(2, ns_a, ns_b, fast2{});
+                    row_passes(2, ns_a, ns_b, rows_more, fast2{});
                     band_update(2, last_m0, last_mp, std::true_type{}, ns_a, ns_b);
                     log_row(2, std::true_type{});
                     lin_l += row_bytes;
-                    rows_left = ended ? -1 : rows_left;
+                    rows_more -= 1;
                     __builtin_amdgcn_wave_barrier();
                 }
                 if (ended) break;
-                if (rows_left <= 0 || ns_a > lim_a || ns_b > lim_b) break;
+                if (rows_more < 0 || ns_a > lim_a || ns_b > lim_b) break;
                 const int ns_max = max(ns_a, ns_b);
                 if (ns_max < 64) continue;                   // back to the two loops above
                 // a half with 64 slots or more (0.01 % of the rows): the general form
-                rows_left -= 1;
-                rows_run += 1;
                 NJ = (ns_max + 31) >> 5;
                 DWS_ROW(~0ull, ns_a, ns_b, NJ);
-                row_passes(NJ, ns_a, ns_b, fast0{});
+                row_passes(NJ, ns_a, ns_b, rows_more, fast0{});
+                rows_more -= 1;
                 lin_l += row_bytes;
                 if ((ns_max & 31) == 0) ring_st(rbase, lin_l - 2u * sl - 2u, sepv);      // a half fills its last pass: no idle lane for the entry behind its row
                 band_update(NJ, last_m0, last_mp, std::true_type{}, ns_a, ns_b);
@@ -567,10 +603,11 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 __builtin_amdgcn_wave_barrier();
             }
             // every exit of the loop comes by here: a row that reached an end is not counted (the end-of-block code below counts it)
-            d += rows_run - (ended ? 1 : 0);
+            d += rows_left - 1 - rows_more_value(rows_more, ended != 0) - (ended ? 1 : 0);
         } else {
             // one half is between blocks (or out of units) while the other one rows on: the general form of everything
             const int slot_lim = (band_tol2 >> 1) + 1;
+            int no_count = 0;      // (row_passes marks its caller's count-down when a row reaches an end: this loop has none and tests `ended`)
             while (true) {
                 // the two conditions as masks (a ballot of their conjunction makes the compiler turn the mask into a 0/1 vector and
                 // compare it again)
@@ -579,7 +616,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 const int ns_max = max(ns_a, ns_b);
                 NJ = (ns_max + 31) >> 5;
                 DWS_ROW(rmask, ns_a, ns_b, NJ);
-                row_passes(NJ, ns_a, ns_b, std::integral_constant<int, 0>{});
+                row_passes(NJ, ns_a, ns_b, no_count, std::integral_constant<int, 0>{});
                 lin_l += row_bytes;
                 if ((ns_max & 31) == 0) ring_st(rbase, lin_l - 2u * sl - 2u, sepv);
                 band_update(NJ, last_m0, last_mp, std::false_type{}, ns_a, ns_b);
