@@ -21,9 +21,12 @@
 // unit as one packed word per half (profiles/dw_row_trims.md); the code around the row loops works in base units.
 // A snake step makes one compare, nn == what is left of the window, and looks closer only when an active lane has it (snake_step_end);
 // idle lanes are not parked, every consumer masks them (profiles/dw_snake_compare.md).
+// The staged words of a workgroup's eight halves are interleaved word-major, so that a window's byte offset is its doubled position with
+// the low five bits cleared (match16_le2), and the entry between two rows is kept in a register whose upper half is large and negative
+// (sep_word), so that one select per pass serves the ring store and x + y (profiles/dw_staging.md).
 // 64 VGPRs, 19 KB of LDS per four waves, eight waves per SIMD (tests/test_dw_resources_cpu.py holds the compiler to it); on its common
-// path a one-pass dual row is 46 VALU (138 issue cycles) + 25 SALU, a two-pass row 77 (232) + 46 (tests/test_dw_row_cycles_cpu.py caps
-// the cycles, counting the rare part of the snake step too: 142 / 240); VALU-issue bound (profiles/r03_dw_row_breakdown.md,
+// path a one-pass dual row is 43 VALU (130 issue cycles) + 25 SALU, a two-pass row 71 (216) + 46 (tests/test_dw_row_cycles_staging_cpu.py
+// caps the cycles, counting the rare part of the snake step too: 134 / 224); VALU-issue bound (profiles/r03_dw_row_breakdown.md,
 // r05_dw_attempt.md).  The code between two row loops is 10 % of a wave's life (profiles/dw_block_setup.md).  What is and is not
 // settled about the row loops: DESIGN.md §6.
 #include <stdio.h>
@@ -47,10 +50,13 @@ constexpr int FULL_BAND_TOL = (int)(0.3 * SEG_BLK), FULL_MAX_D = (int)(.3 * (SEG
 // reads the furthest x of diagonals k - 1 and k + 1 of row d - 1 straight from that row's entries in the ring, at pbase + tt and
 // pbase + tt + 1 (inside the band they are entries of that row; at its two edges the entry between rows or a dropped diagonal: see
 // the start point in row_passes).
-struct HalfLds {
-    uint32_t Qp[SEQ_WORDS2];
-    uint32_t Tp[SEQ_WORDS2];
+// The staged words of a workgroup's eight halves are interleaved word-major (match16_le2): word w of half u = 2 wave + half at
+// Qp[w][u] / Tp[w][u], 384 bytes per half as before.
+struct StagedLds {
+    uint32_t Qp[SEQ_WORDS2][AL_WAVES * 2];
+    uint32_t Tp[SEQ_WORDS2][AL_WAVES * 2];
 };
+#define STAGED_T_BYTES ((int)offsetof(StagedLds, Tp))
 // The ring of d-rows of a half: 16-bit rows of doubled x packed back to back, wrapping (in front of row 0: -2, 0, -2, see the block set-up).
 // It is its own 2 KB-aligned LDS array so that the address of ring byte position p is `base | (p & 0x7fe)`: one v_and_or_b32.
 // Positions (lin, pbase, rlin) are kept in bytes.
@@ -58,6 +64,12 @@ typedef __attribute__((address_space(3))) uint16_t lds_u16_t;
 typedef __attribute__((address_space(3))) int16_t lds_i16_t;
 __device__ __forceinline__ int ring_ld(uint32_t base, uint32_t pos) { return (int)*(lds_i16_t*)(uintptr_t)(base | (pos & (2 * RCAP - 2))); }
 __device__ __forceinline__ void ring_st(uint32_t base, uint32_t pos, int x) { *(lds_u16_t*)(uintptr_t)(base | (pos & (2 * RCAP - 2))) = (uint16_t)x; }
+
+// The entry between two rows, as the register that idle lanes select (sepv): rec = slots of the row | left cut of the row before << 8, below
+// 2^15.  The low 16 bits — all that is stored in the ring and all a reader sees — are ~rec, a negative 16-bit number; the upper half makes
+// the whole register about -2^29, so that an idle lane's x + y, formed from it, never reaches a band threshold or a row maximum without a
+// select of its own.  One v_xor_b32 with a literal, where ~rec was one v_not_b32.
+__device__ __forceinline__ int sep_word(int rec) { return rec ^ (int)0xE000FFFFu; }
 
 // mask of the lanes where p holds, without the bool -> int -> compare round trip of __ballot
 #define BALLOT(p) __builtin_amdgcn_ballot_w64(p)
@@ -150,11 +162,19 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                                                        DwHandover* __restrict__ hand, unsigned int* __restrict__ hand_count,
                                                        unsigned int* __restrict__ cursor, unsigned long long* __restrict__ counters,
                                                        const CnsFwdArgs ca) {
-    __shared__ HalfLds lds[AL_WAVES][2];
-    __shared__ __attribute__((aligned(2 * RCAP))) uint16_t rings[AL_WAVES * 2][RCAP];
+    // one object, so that the staged words sit behind the 16 KB of rings, which is 2 KB-aligned (match16_le2 ORs a window's offset into
+    // the address), and the workgroup's LDS stays 19 456 bytes whatever order the compiler would give two arrays
+    struct DwLds {
+        uint16_t rings[AL_WAVES * 2][RCAP];
+        StagedLds staged;
+    };
+    static_assert(offsetof(DwLds, staged) % 2048 == 0 && 32 * SEQ_WORDS2 <= 2048 && sizeof(uint32_t) * AL_WAVES * 2 == 32,
+                  "a window's byte offset x2 & ~31 and the address of a half's word 0 have no bit in common");
+    __shared__ __attribute__((aligned(2 * RCAP))) DwLds lds;
     const int lane = lane_id(), hh = lane >> 5, sl = lane & 31;
-    HalfLds& S = lds[threadIdx.x >> 6][hh];
-    const uint32_t rbase = (uint32_t)(uintptr_t)(lds_u16_t*)&rings[(threadIdx.x >> 6) * 2 + hh][0];
+    const int half_u = (threadIdx.x >> 6) * 2 + hh;
+    const uint32_t rbase = (uint32_t)(uintptr_t)(lds_u16_t*)&lds.rings[half_u][0];
+    const uint32_t ubase = (uint32_t)(uintptr_t)(lds_u32_t*)&lds.staged.Qp[0][half_u];      // the half's word 0 of the query (match16_le2)
     unsigned int cells = 0, nblocks = 0, nhand = 0;
 #ifdef MECAT_DW_STATS
     // development build only (tools/dev/dw_breakdown.sh -> profiles/rNN_dw_row_breakdown.md): where the wave's time and rows go.
@@ -187,7 +207,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
     // band = nslot diagonals from min_k; d = rows done.  The three values every lane adds its own 2 * sl to on every row are kept with
     // it added (`_l`: per lane): the row code then uses them as they are, and the band update moves all lanes by the same amount.
     int best_m = -1, mk_l = 0, nslot = 0, aligned = 0, end_x = 0, end_k = 0, end_d = 0, end_mk = 0, d = 0;
-    int sepv = -1;              // what idle lanes store behind the row: ~(slots of the row | left cut of the row before << 8), see row_passes
+    int sepv = sep_word(1);     // what idle lanes store behind the row: sep_word(slots of the row | left cut of the row before << 8), see row_passes
     int cut = 0;                // diagonals the last band update dropped on the left (`first`)
     unsigned int lin_l = 0;     // ring position behind the last row (bytes, like the next two) + 2 sl
     unsigned int pb_l = 0;      // ring position of the previous row's entry for diagonal (this row's min_k) - 1, + 2 sl
@@ -260,7 +280,8 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                     max_d = (int)(.3 * (qblk + tblk));
                 } else { qblk = SEG_BLK; tblk = SEG_BLK; last_block = 0; band_tol = FULL_BAND_TOL; max_d = FULL_MAX_D; }      // no f64 for a full block
                 }
-                // Staging: word w = logical bases 16w .. 16w+15, first base in the low bits.  Only the words that hold a base of the
+                // Staging: word w = logical bases 16w .. 16w+15, first base in the low bits, in the half's own column of the interleaved
+                // array (a live window stays in it: its words are below SEQ_WORDS2, so the OR of match16_le2 is an add).  Only the words that hold a base of the
                 // block are written (16 w < blk); the others keep what an earlier block left there, and no result depends on it:
                 // a live diagonal has x <= q_len and its window is words x >> 4 and (x >> 4) + 1, so every base it sees at or beyond
                 // q_len (t_len for the target) sits at window offset >= lim = min(q_len - x, t_len - y).  A first difference in
@@ -272,15 +293,16 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 const int trips = BALLOT(max(qblk, tblk) > 512) ? 2 : 1;
 #pragma unroll 1
                 for (int w = sl, i = 0; i < trips; w += 32, ++i) {      // (blk <= 1.2 * (SEG_BLK + 99): 16 w < blk keeps w below SEQ_WORDS2)
-                    if (w * 16 < qblk) S.Qp[w] = view_word_le(q, qidx + w * 16);
-                    if (w * 16 < tblk) S.Tp[w] = view_word_le(t, tidx + w * 16);
+                    lds_u32_t* const sw = (lds_u32_t*)(uintptr_t)(ubase + 32u * (unsigned)w);      // Qp[w][u]; Tp[w][u] is STAGED_T_BYTES behind it
+                    if (w * 16 < qblk) sw[0] = view_word_le(q, qidx + w * 16);
+                    if (w * 16 < tblk) sw[STAGED_T_BYTES / 4] = view_word_le(t, tidx + w * 16);
                 }
                 // The reference zero-fills V per block (:232-233); row d only reads diagonals written by row d - 1, except row 0,
                 // which reads V[k_offset - 1] and V[k_offset + 1]: the two zeros in front of row 0.
                 // Between two rows of the ring sits one entry of -2 or less (see the start point below); in front of row 0: -2, 0, -2 — row 0
                 // reads the first two (x2 = max(-2 + 2, 0) = 0), row 1 reads the third as the entry "left of row 0".
                 if (sl < 3) ring_st(rbase, 2u * sl, sl == 1 ? 0 : -2);
-                best_m = -2; mk_l = 4 * sl; nslot = 1; sepv = ~1; cut = 0;
+                best_m = -2; mk_l = 4 * sl; nslot = 1; sepv = sep_word(1); cut = 0;
                 aligned = 0; end_x = 0; end_k = 0; end_d = 0; d = 0;
                 lin_l = 6u + 2u * sl; pb_l = 2u * sl; rlin_l = 2u * sl;
                 dlim = max_d; inblock = true;
@@ -316,7 +338,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
             // the row maximum qualifies, and the row maximum is the running maximum (x + y grows by at least one per row along
             // the best path, which the band never prunes).
             int first, last;
-            int pk = 0;      // BOTH, NJ <= 2: (new slot count | first << 8) of the lane's half, which is the next row's separator but for a NOT
+            int pk = 0;      // BOTH, NJ <= 2: (new slot count | first << 8) of the lane's half, which is the next row's separator but for sep_word's XOR
             if (NJ == 1) {
                 // 32 diagonals per half: one ballot; first / last set bit of the half's 32 bits with the raw instructions
                 // (v_ffbl / v_ffbh return -1 for an empty mask: a half without a block, whose values are not used)
@@ -395,13 +417,14 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 cut = first;
                 // what the idle lanes of the next row store behind it: its slot count and this cut, as a negative 16-bit number — which is
                 // all the start point needs of the entry between two rows.  With both halves in a row of one or two passes that is the
-                // packed word, inverted (a cut below 64).  Otherwise the cut is kept to 7 bits, saturating: the tail traceback hands a
-                // block over when it meets 127.
-                if (BOTH && NJ <= 2) sepv = ~pk;
+                // packed word, inverted in its low 16 bits (a cut below 64).  Otherwise the cut is kept to 7 bits, saturating: the tail
+                // traceback hands a block over when it meets 127.  Every writer goes through sep_word, which also gives the register the
+                // upper half that idle lanes' x + y is formed from.
+                if (BOTH && NJ <= 2) sepv = sep_word(pk);
                 else {
                     int c7;
                     asm("v_min_u16 %0, 0x7f, %1" : "=v"(c7) : "v"(first));
-                    sepv = ~(nslot | (c7 << 8));
+                    sepv = sep_word(nslot | (c7 << 8));
                 }
             }
             if (!(BOTH && NJ <= 2)) { sa = __builtin_amdgcn_readlane(nslot, 0); sb = __builtin_amdgcn_readlane(nslot, 32); }
@@ -422,6 +445,8 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
 
             row_bytes = twice((unsigned)nslot) + 2u;
             last_ns = nslot;
+            // (-2^30: the identity of the row maximum and "no previous pass" for the band update, both below anything sep_word + y gives
+            // an idle lane; the general band update's recompute from the ring keeps its own select on this value: it reads x, not m0)
             int mmax = -0x40000000, m0 = -0x40000000, mp = -0x40000000;
             int j = 0;
             do {                                 // at least one pass (a pass over an empty band only moves idle lanes)
@@ -469,9 +494,13 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 }
                 // 0 <= y <= t_len and x <= q_len on every live diagonal (a diagonal at an end stops the block).
                 // Idle lanes are not parked: they start from whatever max(vl + 2, vr) of the ring gives them (0 .. 65535) and snake on it.
-                // All they do is load — window words from anywhere in or beyond the LDS allocation, where reads return 0 — and nothing
+                // All they do is load.  A window's address is (position & ~31) | ubase plus a constant of at most STAGED_T_BYTES + 32
+                // (match16_le2): for a position of 0 .. 65535 and more, or a negative y, that is some 32-bit number whose low bits are
+                // the half's own column — inside the workgroup's allocation it reads a ring entry or a staged word of this or another
+                // half, beyond it (and wrapped around 2^32: then inside or beyond again) the read returns 0; LDS reads fault nowhere
+                // and nothing is written through such an address.  Nothing
                 // of theirs is kept, each consumer guarding itself: the stored value is `act ? x : sepv` (FAST 0: under tt <= nslot), m0 is
-                // `act ? x + y : -inf` (so neither the row maximum nor the band update sees them), snake_step_end masks the lanes at
+                // that value + y, about -2^29 on an idle lane (so neither the row maximum nor the band update sees them), snake_step_end masks the lanes at
                 // their limit with amask — an idle lane neither asks for a further step nor ends a block —, and the CNS flag bits are
                 // masked by the reader with the row's slot count.  Nothing behind the passes reads a lane's x, y, limc or nn.
                 int y = x - k2;
@@ -488,16 +517,19 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                     asm("v_min3_i32 %0, %1, %2, 32" : "=v"(limc) : "v"(q_len2 - x), "v"(t_len2 - y));
                     // 0..15 equal bases (doubled: 0..30), or >= 16 (0x7ffffffe) when the whole window matches.  A lane with exactly 16
                     // bases left that all match asks for one more step, which then moves nothing.
-                    const int m = match16_le2(S.Qp, x, S.Tp, y);
+                    const int m = match16_le2<STAGED_T_BYTES>(ubase, x, y);
                     const int nn = min(m, limc);
                     // one compare per step: nn == limc holds exactly on the lanes that go on (limc == 32) or have nothing left of the
                     // query or of the target on their diagonal (limc < 32); which of the two is looked at only when an active lane has it
                     x += nn; y += nn;
                     more = snake_step_end(BALLOT(nn == limc), amask, nn, ended, rows_more);
                 } while (more);
-                if (NJ <= 2 || tt <= nslot) ring_st(rbase, lin_l + 64u * (unsigned)j, act ? x : sepv);
+                // one select per pass: the ring takes the low 16 bits of v, and an idle lane's m0 = sepv + y is about -2^29 (sep_word; its
+                // y is within +-2^17: x from 16 bits of the ring plus its snake, k2 a diagonal of the block)
+                const int v = act ? x : sepv;
+                if (NJ <= 2 || tt <= nslot) ring_st(rbase, lin_l + 64u * (unsigned)j, v);
                 mp = m0;
-                m0 = act ? x + y : -0x40000000;     // also read by the band update (NJ <= 2); idle lanes never qualify
+                m0 = v + y;                         // also read by the band update (NJ <= 2); idle lanes never qualify
                 mmax = NJ == 1 ? m0 : max(mmax, m0);
             } while (++j < NJ);
             last_m0 = m0; last_mp = mp;
@@ -850,7 +882,8 @@ int dw_extend2_launch(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* re
     if (getenv("MECAT_TRACE")) {
         int nb = 0;
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dw_extend2<false>, AL_BLOCK, 0);
-        fprintf(stderr, "[dw trace] occupancy query: %d blocks of %d threads per CU; grid %d; HalfLds %zu bytes\n", nb, AL_BLOCK, grid, sizeof(HalfLds));
+        fprintf(stderr, "[dw trace] occupancy query: %d blocks of %d threads per CU; grid %d; staged words %zu bytes per half\n", nb, AL_BLOCK, grid,
+                sizeof(StagedLds) / (AL_WAVES * 2));
     }
     CnsFwdArgs none;
     memset(&none, 0, sizeof(none));

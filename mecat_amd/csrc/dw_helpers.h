@@ -125,9 +125,19 @@ __device__ __forceinline__ int match16_le(const uint32_t* Q, int x, const uint32
 // the v_alignbit shift operand (2 x modulo 32), so the two adds of match16_le go.  The result is in doubled units too: the bit index of
 // the first difference with its lowest bit cleared (2 * (tz >> 1)); the sign bit is cleared with it, so that 16 equal bases (v_ffbl_b32
 // of 0 is -1) still read as a large positive number, 0x7ffffffe.  Callers clamp with min3(.., lim2, 32).
-__device__ __forceinline__ int match16_le2(const uint32_t* Q, int x2, const uint32_t* T, int y2) {
-    const int wq = x2 >> 5, wt = y2 >> 5;
-    const uint32_t d = __builtin_amdgcn_alignbit(Q[wq + 1], Q[wq], (uint32_t)x2) ^ __builtin_amdgcn_alignbit(T[wt + 1], T[wt], (uint32_t)y2);
+// The staged words of the eight half-waves of a workgroup are interleaved word-major: word w of half u at dword 8 w + u of the query's
+// region, the target's region T_BYTES behind it.  Consecutive words of one half are then 32 bytes apart, and 32 is what a word is in
+// doubled positions: x2 & ~31 IS the byte offset of word x2 >> 5 — no shift.  ubase: the LDS address of the half's word 0 of the query
+// (region base + 4 u); the region is 2 KB-aligned and a live x2 & ~31 is below 2048, so the two have no bit in common and the window's
+// address is one v_and_or_b32, for the target too: its two words are read at the constant offsets T_BYTES and T_BYTES + 32 from the
+// address formed the same way.  T_BYTES is beyond the reach of ds_read2_b32's offsets, hence two single reads — volatile, because the
+// compiler otherwise pairs them behind a v_add_u32 of the base, which gives two of the four cycles back (the second-base-register form,
+// v_and_b32 + v_add_u32 and a ds_read2_b32, measured 4.5 ms per step slower: profiles/dw_staging.md).
+typedef __attribute__((address_space(3))) uint32_t lds_u32_t;
+template <int T_BYTES> __device__ __forceinline__ int match16_le2(uint32_t ubase, int x2, int y2) {
+    const lds_u32_t* Q = (const lds_u32_t*)(uintptr_t)(((uint32_t)x2 & ~31u) | ubase);
+    const volatile lds_u32_t* T = (const volatile lds_u32_t*)(uintptr_t)(((uint32_t)y2 & ~31u) | ubase);
+    const uint32_t d = __builtin_amdgcn_alignbit(Q[8], Q[0], (uint32_t)x2) ^ __builtin_amdgcn_alignbit(T[T_BYTES / 4 + 8], T[T_BYTES / 4], (uint32_t)y2);
     uint32_t tz;
     asm("v_ffbl_b32 %0, %1" : "=v"(tz) : "v"(d));
     return (int)(tz & 0x7ffffffeu);
