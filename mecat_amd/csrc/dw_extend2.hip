@@ -24,10 +24,13 @@
 // The staged words of a workgroup's eight halves are interleaved word-major, so that a window's byte offset is its doubled position with
 // the low five bits cleared (match16_le2), and the entry between two rows is kept in a register whose upper half is large and negative
 // (sep_word), so that one select per pass serves the ring store and x + y (profiles/dw_staging.md).
+// The scalar side of a row is kept as short as its vector side (the kernel ran at 78 % of the device's scalar issue rate,
+// profiles/dw_scalar_side.md): a two-pass row takes the lane masks of both passes from one s_bfm_b64 per half (pass_bits), and the band
+// update puts its 64-bit words together by moves (pair64) and takes a half's slot count from one sum.
 // 64 VGPRs, 19 KB of LDS per four waves, eight waves per SIMD (tests/test_dw_resources_cpu.py holds the compiler to it); on its common
-// path a one-pass dual row is 43 VALU (130 issue cycles) + 25 SALU, a two-pass row 71 (216) + 46 (tests/test_dw_row_cycles_staging_cpu.py
-// caps the cycles, counting the rare part of the snake step too: 134 / 224); VALU-issue bound (profiles/r03_dw_row_breakdown.md,
-// r05_dw_attempt.md).  The code between two row loops is 10 % of a wave's life (profiles/dw_block_setup.md).  What is and is not
+// path a one-pass dual row is 43 VALU (130 issue cycles) + 25 SALU, a two-pass row 71 (216) + 33 (tests/test_dw_row_cycles_staging_cpu.py
+// caps the cycles, counting the rare part of the snake step too: 134 / 224; tests/test_dw_row_scalar_cpu.py the scalar instructions, 31 /
+// 45 as listed); VALU-issue bound (profiles/r03_dw_row_breakdown.md, r05_dw_attempt.md).  The code between two row loops is 10 % of a wave's life (profiles/dw_block_setup.md).  What is and is not
 // settled about the row loops: DESIGN.md §6.
 #include <stdio.h>
 #include <stdlib.h>
@@ -99,6 +102,25 @@ __device__ __forceinline__ int half_min(int v) { return -half_max(-v); }
 template <int OFF> __device__ __forceinline__ unsigned long long bits_at(int n) {
     unsigned long long r;
     asm("s_bfm_b64 %0, %1, %2" : "=s"(r) : "s"(n), "n"(OFF));
+    return r;
+}
+
+// Two 32-bit scalar values as one 64-bit value, low word first.  Written as a two-element vector, which the compiler builds by placing the
+// two words in a register pair (at most two s_mov_b32); `(uint64_t)hi << 32 | lo` and its masked 64-bit forms it lowers to zero-extensions
+// through a zero register and an s_or_b64.
+typedef uint32_t dw_u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned long long pair64(uint32_t lo, uint32_t hi) {
+    const dw_u32x2 v = {lo, hi};
+    return __builtin_bit_cast(unsigned long long, v);
+}
+__device__ __forceinline__ uint32_t word_lo(unsigned long long v) { return __builtin_bit_cast(dw_u32x2, v).x; }
+__device__ __forceinline__ uint32_t word_hi(unsigned long long v) { return __builtin_bit_cast(dw_u32x2, v).y; }
+
+// The lane masks of both passes of a two-pass row of one half: the low n bits of 64 (s_bfm_b64 takes six bits of n: 0 <= n <= 63).  The
+// low word is the half's pass-1 mask, min(n, 32) bits, the high word its pass-2 mask, max(n - 32, 0) bits: no clamp, no subtraction.
+__device__ __forceinline__ unsigned long long pass_bits(int n) {
+    unsigned long long r;
+    asm("s_bfm_b64 %0, %1, 0" : "=s"(r) : "s"(n));
     return r;
 }
 
@@ -184,6 +206,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
     unsigned long long nh[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // unit rows by band width: <= 8, 16, 24, 32, 48, 64, 96, more
     unsigned long long q16[6] = {0, 0, 0, 0, 0, 0};           // unit rows by ceil(nslot / 16): 1, 2, 3, 4, 5-6, more
     unsigned long long snake2 = 0;                            // snake steps beyond the first (per pass)
+    unsigned long long n_one = 0, n_one32 = 0;               // dual rows of at most 32 slots per half with both halves in a block; those with a half at exactly 32
     const unsigned long long tk_start = wall_clock64();
 #define DWS_T(var) const unsigned long long var = wall_clock64()
 #define DWS_ADD(acc, a, b) acc += (b) - (a)
@@ -373,11 +396,12 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                     // first / last qualifying diagonal of each half on the scalar unit (its 64 bits: the half's word of both ballots),
                     // handed to the lanes as one packed value per half: two moves and a select instead of two 64-bit shifts, four
                     // find-first / find-last and their merge
-                    const unsigned long long wa = (q0 & 0xffffffffull) | (q1 << 32), wb = (q0 >> 32) | (q1 & 0xffffffff00000000ull);
+                    // (the words put together from 32-bit halves, four moves: pair64.  Slots = last - first + 2 with last = 63 - clz, as one
+                    // sum taken from 65, the way the one-pass row does it)
+                    const unsigned long long wa = pair64(word_lo(q0), word_lo(q1)), wb = pair64(word_hi(q0), word_hi(q1));
                     const int fa = __builtin_ctzll(wa), fb = __builtin_ctzll(wb);
-                    const int la = 63 - __builtin_clzll(wa), lb = 63 - __builtin_clzll(wb);
-                    sa = la - fa + 2;
-                    sb = lb - fb + 2;
+                    sa = 65 - (fa + __builtin_clzll(wa));
+                    sb = 65 - (fb + __builtin_clzll(wb));
                     // (new slot count, first: last = first + slots - 2; kept packed: the compiler would select the four values one by one)
                     unsigned long long pkw = (unsigned int)(sa | (fa << 8)) | ((unsigned long long)(unsigned int)(sb | (fb << 8)) << 32);
                     asm("" : "+s"(pkw));
@@ -448,6 +472,14 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
             // (-2^30: the identity of the row maximum and "no previous pass" for the band update, both below anything sep_word + y gives
             // an idle lane; the general band update's recompute from the ring keeps its own select on this value: it reads x, not m0)
             int mmax = -0x40000000, m0 = -0x40000000, mp = -0x40000000;
+            // FAST 2: the lane masks of both passes.  The low ns bits of 64, one s_bfm_b64 per half (pass_bits; ns <= 63), are the half's pass-1
+            // mask in the low word and its pass-2 mask in the high word; the wave's mask of a pass is the two halves' words of it side by side.
+            unsigned long long two_m1 = 0, two_m2 = 0;
+            if (FAST == 2) {
+                const unsigned long long ma = pass_bits(ns_a), mb = pass_bits(ns_b);
+                two_m1 = pair64(word_lo(ma), word_lo(mb));
+                two_m2 = pair64(word_hi(ma), word_hi(mb));
+            }
             int j = 0;
             do {                                 // at least one pass (a pass over an empty band only moves idle lanes)
                 const int tt = sl + 32 * j;
@@ -455,8 +487,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 // slot counts and used as the lane predicate as it is
                 unsigned long long amask;
                 if (FAST == 2) {
-                    amask = j == 0 ? (bits_at<0>(min(ns_a, 32)) | bits_at<32>(min(ns_b, 32)))
-                                   : (bits_at<0>(max(ns_a, 32) - 32) | bits_at<32>(max(ns_b, 32) - 32));
+                    amask = j == 0 ? two_m1 : two_m2;
                 } else if (FAST == 1) {
                     amask = bits_at<0>(ns_a) | bits_at<32>(ns_b);
                 } else {
@@ -545,6 +576,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
             nidle += (rmask == ~0ull) ? 0u : 1u;
             nwide += NJ > 1 ? 1u : 0u;
             n_pass3 += NJ > 2 ? 1u : 0u;
+            if (rmask == ~0ull && max(ns_a, ns_b) <= 32) { n_one += 1; n_one32 += max(ns_a, ns_b) == 32 ? 1u : 0u; }
             for (int hq = 0; hq < 2; ++hq) {
                 if (!((rmask >> (hq << 5)) & 1ull)) continue;      // the half is not rowing
                 const int ns = hq ? ns_b : ns_a;
@@ -592,7 +624,8 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
             // may run behind the current one, which is also the loops' bound; a row that reached an end marks it (snake_step_end).
             int rows_more = rows_left - 1;
             while (true) {
-                // one-pass rows (rows left, and both slot counts within their limits: one sign test)
+                // one-pass rows (rows left, and both slot counts within their limits: one sign test; why the `full` test stays in the
+                // loop: profiles/dw_scalar_side.md, S3)
                 while ((rows_more | (one_a - ns_a) | (one_b - ns_b)) >= 0) {
                     DWS_ROW(~0ull, ns_a, ns_b, 1);
                     const bool full = ((ns_a | ns_b) & 32) != 0;       // a half has all of its 32 lanes on diagonals: nobody stores the entry
@@ -868,6 +901,8 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
         atomicAdd(&counters[25], n_pass3);
         atomicAdd(&counters[26], 1ull);                           // waves
         atomicAdd(&counters[27], snake2);
+        atomicAdd(&counters[28], n_one);
+        atomicAdd(&counters[29], n_one32);
         for (int i = 0; i < 8; ++i) atomicAdd(&counters[32 + i], nh[i]);
         for (int i = 0; i < 6; ++i) atomicAdd(&counters[40 + i], q16[i]);
 #endif

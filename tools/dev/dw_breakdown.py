@@ -36,6 +36,8 @@ print()
 print("dual rows %d (%.1f per outer iteration, %d outer iterations, %.1f %% of them with a set-up, %.1f %% ended a block)" % (rows, rows / n_outer, n_outer, 100.0 * n_setup / n_outer, 100.0 * n_ended / n_outer))
 print("dual rows with one idle half %.1f %%, with a second pass %.1f %%, with three or more %.2f %%; cells per dual row %.1f; extra snake steps per pass %.4f"
       % (100.0 * idle / rows, 100.0 * wide / rows, 100.0 * n_pass3 / rows, c["dw_cells"] / rows, snake2 / max(1, rows)))
+n_one, n_one32 = D[28], D[29]
+print("dual rows with both halves in a block and at most 32 slots in each: %d, %.2f %% of them with a half at exactly 32 slots" % (n_one, 100.0 * n_one32 / max(1, n_one)))
 ur = sum(nh)
 print()
 print("| band width of a unit row | <= 8 | <= 16 | <= 24 | <= 32 | <= 48 | <= 64 | <= 96 | more |")
