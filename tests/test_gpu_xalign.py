@@ -124,7 +124,8 @@ def test_cli_m4_nanopore_mode(tmp_path):
 def test_xdrop_wide_windows_low_complexity(hip, ctx, capfd):
     """Homopolymer / short-period tandem stretches keep hundreds of cells within X of the best score: those blocks leave the
     128-cell ring for the wide-window code — in place, on the wave's global state (the default), or handed to a second launch
-    (MECAT_XD_HANDOVER=1, the round-1 arrangement).  Both == the oracle == the WIDE instantiation run on every block."""
+    (MECAT_XD_HANDOVER=1, the hand-over arrangement: the rest of such a unit's blocks through the wide block).  Both == the
+    oracle == the wide block run on every block (MECAT_XD_WIDE=1, the all-wide arrangement)."""
     rng = np.random.default_rng(4242)
     O = H.orc()
     xa = O.orc_xaligner_new()
