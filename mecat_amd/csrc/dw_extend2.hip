@@ -12,9 +12,13 @@
 // first diagonal and the two ring positions with the lane's own offset already added); what steers the row loops — rows left, slot
 // counts, lane masks of a pass — lives on the scalar unit.  Per-half row maxima: four mirrored DPP steps + v_permlane16_swap;
 // first / last qualifying diagonal of the band update from the two 32-bit halves of a ballot.  d-rows live in a 1024-entry
-// circular buffer per half, packed back to back with one entry between two rows that is the row record (see row_passes): ~37 rows
-// stay traceable; the rare block whose tail traceback needs an overwritten row, or that never reached an end of either sequence,
-// is handed over to the one-unit kernel (dw_extend), which keeps every row: 0.5 % of the units.
+// ring per half, packed back to back with one entry between two rows that is the row record (see row_passes).  Ring positions are LDS
+// addresses and a row never straddles the ring's end — the row that would, about one in 36, starts at the ring's origin instead, where
+// three reserved entries link it to the row in front (ring_relocate; the two fast loops leave through their bound for it) —, so the row
+// code reads and writes at the positions as they are, the right neighbour and pass 2 by the instruction's offset, where every access had
+// a v_and_or_b32 to wrap a byte counter (profiles/dw_ring_linear.md).  ~35 rows stay traceable; the rare block whose tail traceback
+// needs an overwritten row, or that never reached an end of either sequence, is handed over to the one-unit kernel (dw_extend), which
+// keeps every row: 0.5 % of the units.
 // Snake steps compare 16 bases per v_alignbit pair on blocks staged little-endian (view_word_le); one-pass (58 %) and two-pass rows
 // have loop bodies of their own.  Inside a block the row code keeps positions in doubled units (2 x is its own v_alignbit shift operand),
 // counts the rows of the two fast loops on the scalar unit, and takes the band update's first diagonal and slot count from the scalar
@@ -28,9 +32,9 @@
 // profiles/dw_scalar_side.md): a two-pass row takes the lane masks of both passes from one s_bfm_b64 per half (pass_bits), and the band
 // update puts its 64-bit words together by moves (pair64) and takes a half's slot count from one sum.
 // 64 VGPRs, 19 KB of LDS per four waves, eight waves per SIMD (tests/test_dw_resources_cpu.py holds the compiler to it); on its common
-// path a one-pass dual row is 43 VALU (130 issue cycles) + 25 SALU, a two-pass row 71 (216) + 33 (tests/test_dw_row_cycles_staging_cpu.py
-// caps the cycles, counting the rare part of the snake step too: 134 / 224; tests/test_dw_row_scalar_cpu.py the scalar instructions, 31 /
-// 45 as listed); VALU-issue bound (profiles/r03_dw_row_breakdown.md, r05_dw_attempt.md).  The code between two row loops is 10 % of a wave's life (profiles/dw_block_setup.md).  What is and is not
+// path a one-pass dual row is 40 VALU (120 issue cycles) + 27 SALU, a two-pass row 62 (188) + 35 (tests/test_dw_ring_linear_cpu.py
+// caps the cycles, counting the rare part of the snake step too: 124 / 196; tests/test_dw_row_scalar_cpu.py the scalar instructions, 33 /
+// 47 as listed); VALU-issue bound (profiles/r03_dw_row_breakdown.md, r05_dw_attempt.md).  The code between two row loops is 10 % of a wave's life (profiles/dw_block_setup.md).  What is and is not
 // settled about the row loops: DESIGN.md §6.
 #include <stdio.h>
 #include <stdlib.h>
@@ -60,13 +64,26 @@ struct StagedLds {
     uint32_t Tp[SEQ_WORDS2][AL_WAVES * 2];
 };
 #define STAGED_T_BYTES ((int)offsetof(StagedLds, Tp))
-// The ring of d-rows of a half: 16-bit rows of doubled x packed back to back, wrapping (in front of row 0: -2, 0, -2, see the block set-up).
-// It is its own 2 KB-aligned LDS array so that the address of ring byte position p is `base | (p & 0x7fe)`: one v_and_or_b32.
-// Positions (lin, pbase, rlin) are kept in bytes.
+// The ring of d-rows of a half: 16-bit rows of doubled x packed back to back (in front of row 0: -2, 0, -2, see the block set-up).
+// Positions (lin, pbase, rlin) are LDS byte addresses and a row never straddles the ring's end, so every access of the row code is a
+// ds_read_i16 / ds_write_b16 of the position as it is, the second pass and the right neighbour by the instruction's immediate offset:
+// no address arithmetic per access (profiles/dw_ring_linear.md).  A row that would not fit in front of the end — a row of one or two
+// passes stores ROW_STORE bytes from its start whatever its slots, a wider one its own extent — is relocated to the ring's origin
+// instead (ring_relocate, about once in 36 rows of a half), where three entries are reserved:
+//   entries 0 and 1, one 32-bit word: the link — the ring offset of the entry behind the last row in front of the relocation — in its
+//     low 11 bits, above it the skew — the entries skipped by this block's relocations, for `cells`;
+//   entry 2: a copy of that entry behind the last row, so that the relocated row, which starts at entry RING_ORG = 3, has "the entry
+//     left of the row" where every row has it.
+// The tail traceback steps from a row at entry RING_ORG (row 0 of a block starts at entry 6: never there) to the row in front of it
+// through the link; rows of the lap before stay traceable while they are ROW_STORE bytes ahead of the write point.
+#define RING_ORG 3
+#define ROW_STORE 128u
 typedef __attribute__((address_space(3))) uint16_t lds_u16_t;
 typedef __attribute__((address_space(3))) int16_t lds_i16_t;
-__device__ __forceinline__ int ring_ld(uint32_t base, uint32_t pos) { return (int)*(lds_i16_t*)(uintptr_t)(base | (pos & (2 * RCAP - 2))); }
-__device__ __forceinline__ void ring_st(uint32_t base, uint32_t pos, int x) { *(lds_u16_t*)(uintptr_t)(base | (pos & (2 * RCAP - 2))) = (uint16_t)x; }
+template <int OFF = 0> __device__ __forceinline__ int ring_ld(uint32_t pos) { return (int)((lds_i16_t*)(uintptr_t)pos)[OFF / 2]; }
+template <int OFF = 0> __device__ __forceinline__ void ring_st(uint32_t pos, int x) { ((lds_u16_t*)(uintptr_t)pos)[OFF / 2] = (uint16_t)x; }
+#define RING_LINK_BITS 11
+static_assert(2 * RCAP == 1 << RING_LINK_BITS, "a ring offset is the low bits of the word at the origin");
 
 // The entry between two rows, as the register that idle lanes select (sepv): rec = slots of the row | left cut of the row before << 8, below
 // 2^15.  The low 16 bits — all that is stored in the ring and all a reader sees — are ~rec, a negative 16-bit number; the upper half makes
@@ -195,9 +212,25 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
     __shared__ __attribute__((aligned(2 * RCAP))) DwLds lds;
     const int lane = lane_id(), hh = lane >> 5, sl = lane & 31;
     const int half_u = (threadIdx.x >> 6) * 2 + hh;
-    const uint32_t rbase = (uint32_t)(uintptr_t)(lds_u16_t*)&lds.rings[half_u][0];
+    const uint32_t rbase0 = (uint32_t)(uintptr_t)(lds_u16_t*)&lds.rings[half_u][0];
     const uint32_t ubase = (uint32_t)(uintptr_t)(lds_u32_t*)&lds.staged.Qp[0][half_u];      // the half's word 0 of the query (match16_le2)
-    unsigned int cells = 0, nblocks = 0, nhand = 0;
+    // Ring positions are LDS addresses with the lane's own 2 sl added.  org_l: entry RING_ORG, where a relocated row starts; wrap_l: the
+    // last position a row of one or two passes may start at (its passes store ROW_STORE bytes from there and the entry behind it may take
+    // two more: nothing is ever stored beyond the half's 2 KB — the next half's ring or the staged words sit there).
+    // wrap_l is the one value kept across the row loops: the ring's base is its address bits above the ring's size (RING_BASE, good for any
+    // address inside the ring), and org_l a constant below it.
+    const uint32_t wrap_l = rbase0 + (2u * RCAP - ROW_STORE - 2u) + 2u * sl;
+#define RING_BASE(p) ((p) & ~(2u * RCAP - 1u))
+#define org_l (wrap_l - (2u * RCAP - ROW_STORE - 2u - 2u * RING_ORG))
+    // nev: what a half counts, one kind per lane of one register — lane 0 of the half the units handed over (NEV_HAND), lane 1 the rows
+    // relocated to the ring's origin, lane 2 the tail-walk steps taken through a link, lane 3 the blocks, lane 4 the cells (one register
+    // across the row loops where each count had its own); summed per kind at the kernel's end
+    unsigned int nev = 0;
+    // -128, pass 2's share of y = x - (mk_l + 128), as the result of an asm statement: the compiler then keeps it in a scalar register for the
+    // kernel's life — a plain constant it sets up again inside the two-pass loop, one scalar instruction per row
+    int pass2_k;
+    asm("s_movk_i32 %0, 0xff80" : "=s"(pass2_k));
+    enum { NEV_HAND = 0, NEV_RELOC = 1, NEV_LINK = 2, NEV_BLOCKS = 3, NEV_CELLS = 4 };
 #ifdef MECAT_DW_STATS
     // development build only (tools/dev/dw_breakdown.sh -> profiles/rNN_dw_row_breakdown.md): where the wave's time and rows go.
     // Clocks are s_memrealtime ticks (100 MHz), summed per section over the wave's life; counts are per dual row.
@@ -229,12 +262,13 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
     int q_len2 = 0, t_len2 = 0, last_block = 0, band_tol2 = 0, max_d = 0;
     // band = nslot diagonals from min_k; d = rows done.  The three values every lane adds its own 2 * sl to on every row are kept with
     // it added (`_l`: per lane): the row code then uses them as they are, and the band update moves all lanes by the same amount.
-    int best_m = -1, mk_l = 0, nslot = 0, aligned = 0, end_x = 0, end_k = 0, end_d = 0, end_mk = 0, d = 0;
+    int best_m = -1, mk_l = 0, nslot = 0, d = 0;
     int sepv = sep_word(1);     // what idle lanes store behind the row: sep_word(slots of the row | left cut of the row before << 8), see row_passes
     int cut = 0;                // diagonals the last band update dropped on the left (`first`)
-    unsigned int lin_l = 0;     // ring position behind the last row (bytes, like the next two) + 2 sl
-    unsigned int pb_l = 0;      // ring position of the previous row's entry for diagonal (this row's min_k) - 1, + 2 sl
-    unsigned int rlin_l = 0;    // ring position of the row that ran last, + 2 sl
+    // (ring positions are LDS addresses; a half that never gets a block stores like the others while the other half rows: inside its ring)
+    unsigned int lin_l = org_l + 6u;     // ring position behind the last row (an address, like the next two) + 2 sl
+    unsigned int pb_l = org_l;           // ring position of the previous row's entry for diagonal (this row's min_k) - 1, + 2 sl
+    unsigned int rlin_l = org_l;         // ring position of the row that ran last, + 2 sl
     int dlim = 0;               // rows run while d < dlim: max_d of the block, 0 once an end was reached / without a block
     // CNS: the unit's share of the row log [logpos, logend), the record of the current block's row 0, and whether the unit met something
     // the log cannot hold: more rows than its share, or a row of more than 96 diagonals (a record holds three passes of 32; the pass count is
@@ -324,10 +358,12 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 // which reads V[k_offset - 1] and V[k_offset + 1]: the two zeros in front of row 0.
                 // Between two rows of the ring sits one entry of -2 or less (see the start point below); in front of row 0: -2, 0, -2 — row 0
                 // reads the first two (x2 = max(-2 + 2, 0) = 0), row 1 reads the third as the entry "left of row 0".
-                if (sl < 3) ring_st(rbase, 2u * sl, sl == 1 ? 0 : -2);
+                // They sit behind the three reserved entries at the ring's origin (ring_relocate): the word of entries 0 and 1 is cleared — no
+                // bytes skipped in this block yet —, entry 2 is written by the first relocation.
+                if (sl < 6) ring_st(org_l - 2u * RING_ORG, sl == 3 || sl == 5 ? -2 : 0);
                 best_m = -2; mk_l = 4 * sl; nslot = 1; sepv = sep_word(1); cut = 0;
-                aligned = 0; end_x = 0; end_k = 0; end_d = 0; d = 0;
-                lin_l = 6u + 2u * sl; pb_l = 2u * sl; rlin_l = 2u * sl;
+                d = 0;
+                lin_l = org_l + 6u; pb_l = org_l; rlin_l = org_l;
                 dlim = max_d; inblock = true;
                 q_len2 = 2 * qblk; t_len2 = 2 * tblk; band_tol2 = 2 * band_tol;
                 setup = false;
@@ -348,6 +384,9 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
         // of blocks) needs the position of that maximum and is handed over to dw_extend, like a block whose traceback outran
         // the ring.  The inner loop runs while every half that has a block is still rowing.
         const unsigned long long inmask = BALLOT(inblock);
+        // Where a block reached an end: set by the end-of-block scan below and used up in the same trip — the scan ends the block's rows
+        // (dlim = 0), so its tail walk and accounting follow at once —, so nothing of it is carried across the row loops.  end_d < 0: no end.
+        int end_x = 0, end_k = 0, end_d = -1, end_mk = 0;
         bool row_ok;
         unsigned long long ended = 0;        // lanes whose diagonal reached an end of its block in the row that was just run
         int NJ = 1;
@@ -424,7 +463,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                     const int tt = sl + 32 * j;
                     const bool act = inblock && tt < nslot;
                     const int k2 = mk_l + 128 * j;
-                    const int u = act ? 2 * ring_ld(rbase, rlin_l + 64u * (unsigned)j) - k2 : -0x40000000;      // x2 + y2 = 2 x2 - k2
+                    const int u = act ? 2 * ring_ld(rlin_l + 64u * (unsigned)j) - k2 : -0x40000000;      // x2 + y2 = 2 x2 - k2
                     if (act && u >= best_m - band_tol2) { lo = min(lo, tt); hi = max(hi, tt); }
                 }
                 first = half_min(lo); last = half_max(hi);
@@ -496,7 +535,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 const bool act = __builtin_amdgcn_inverse_ballot_w64(amask);
                 const int k2 = mk_l + 128 * j;                          // (doubled: lane offset 4 sl, 128 per pass)
                 const unsigned int rp = pb_l + 64u * (unsigned)j;       // idle lanes read (and ignore) whatever the ring holds there
-                const int vl = ring_ld(rbase, rp), vr = ring_ld(rbase, rp + 2u);
+                const int vl = ring_ld(rp), vr = ring_ld<2>(rp);
                 // :138-142 `if (k == min_k || (k != max_k && V[k-1] < V[k+1])) x = V[k+1]; else x = V[k-1] + 1;` as max(vl + 1, vr), in
                 // doubled units max(vl + 2, vr): inside the band the two are the same thing (vl < vr <=> vr >= vl + 1).  At k == min_k the
                 // entry on the left is either the entry between two rows — ~(nslot | cut << 8) with nslot >= 1, hence <= -2: vl + 2 <= 0 <=
@@ -534,7 +573,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 // that value + y, about -2^29 on an idle lane (so neither the row maximum nor the band update sees them), snake_step_end masks the lanes at
                 // their limit with amask — an idle lane neither asks for a further step nor ends a block —, and the CNS flag bits are
                 // masked by the reader with the row's slot count.  Nothing behind the passes reads a lane's x, y, limc or nn.
-                int y = x - k2;
+                int y = (FAST == 2 && j == 1) ? (x - mk_l) + pass2_k : x - k2;
 #ifdef MECAT_DW_STATS
                 snake2 -= 1;
 #endif
@@ -558,7 +597,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 // one select per pass: the ring takes the low 16 bits of v, and an idle lane's m0 = sepv + y is about -2^29 (sep_word; its
                 // y is within +-2^17: x from 16 bits of the ring plus its snake, k2 a diagonal of the block)
                 const int v = act ? x : sepv;
-                if (NJ <= 2 || tt <= nslot) ring_st(rbase, lin_l + 64u * (unsigned)j, v);
+                if (NJ <= 2 || tt <= nslot) ring_st(lin_l + 64u * (unsigned)j, v);
                 mp = m0;
                 m0 = v + y;                         // also read by the band update (NJ <= 2); idle lanes never qualify
                 mmax = NJ == 1 ? m0 : max(mmax, m0);
@@ -606,6 +645,32 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 }
             }
         };
+        // The next row of a half (nslot slots, at lin) must not store beyond the ring's end: where it would, the row starts at entry RING_ORG
+        // instead.  The row that ran last stays where it is — pb_l and rlin_l point into it — and the three reserved entries take what a
+        // reader needs to get from the relocated row to it (see the ring's description above).  The entry behind the last row is read
+        // back from the ring: sepv describes the next row by now.  In front of every row outside the two fast loops, which leave
+        // through ring_wraps for it.
+        auto ring_relocate = [&]() __attribute__((always_inline)) {
+            const unsigned int ext = max(twice((unsigned)nslot), ROW_STORE);      // what the row's passes store, see row_passes
+            const bool need = lin_l + (ext - ROW_STORE) > wrap_l;
+            if (BALLOT(need)) {
+                if (need) {
+                    const uint32_t rbase = RING_BASE(wrap_l), lin_u = lin_l - 2u * sl, off = lin_u - rbase;
+                    lds_u32_t* const org = (lds_u32_t*)(uintptr_t)rbase;
+                    const int behind = ring_ld(lin_u - 2u);
+                    const uint32_t skew = (*org >> RING_LINK_BITS) + ((off - 2u * RING_ORG) >> 1);
+                    if (sl == 0) { *org = (off - 2u) | (skew << RING_LINK_BITS); ring_st<4>(rbase, behind); }
+                    lin_l = org_l;
+                    nev += (inblock && sl == NEV_RELOC) ? 1u : 0u;
+                }
+                __builtin_amdgcn_wave_barrier();
+            }
+        };
+        // a half's next row of one or two passes would not fit: all ones in the half's word of the compare, negative as one value
+        auto ring_wraps = [&]() __attribute__((always_inline)) {
+            const unsigned long long w = BALLOT(lin_l > wrap_l);
+            return (int)(word_lo(w) | word_hi(w));
+        };
         int ns_a = __builtin_amdgcn_readlane(nslot, 0), ns_b = __builtin_amdgcn_readlane(nslot, 32);
         if (inmask == ~0ull) {
             // Both halves in a block (98.6 % of the dual rows; it stays that way for as long as the loop runs): the band update writes
@@ -624,24 +689,30 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
             // may run behind the current one, which is also the loops' bound; a row that reached an end marks it (snake_step_end).
             int rows_more = rows_left - 1;
             while (true) {
+                // The two fast loops also run only while the next row of both halves fits in front of the ring's end (ring_wraps: one
+                // vector compare and two scalar instructions per row, in the same sign test).  The rare exit comes by here, the half or
+                // halves are relocated and the loops are entered again.
+                ring_relocate();
+                int wraps = 0;
                 // one-pass rows (rows left, and both slot counts within their limits: one sign test; why the `full` test stays in the
                 // loop: profiles/dw_scalar_side.md, S3)
-                while ((rows_more | (one_a - ns_a) | (one_b - ns_b)) >= 0) {
+                while ((rows_more | (one_a - ns_a) | (one_b - ns_b) | wraps) >= 0) {
                     DWS_ROW(~0ull, ns_a, ns_b, 1);
                     const bool full = ((ns_a | ns_b) & 32) != 0;       // a half has all of its 32 lanes on diagonals: nobody stores the entry
                     row_passes(1, ns_a, ns_b, rows_more, fast1{});     //   behind its row (the other half's idle lane rewrites its own)
                     lin_l += row_bytes;
-                    if (full) ring_st(rbase, lin_l - 2u * sl - 2u, sepv);
+                    if (full) ring_st(lin_l - 2u * sl - 2u, sepv);
                     band_update(1, last_m0, last_mp, std::true_type{}, ns_a, ns_b);
                     log_row(1, std::true_type{});
                     // (a row that reached an end leaves the loop through its bound, which snake_step_end has marked: a second exit makes
                     // the compiler build a machine of flag registers and re-tested branches around every row)
                     rows_more -= 1;
+                    wraps = ring_wraps();
                     __builtin_amdgcn_wave_barrier();
                 }
                 if (ended) break;
                 // two-pass rows: a half has 33 .. 63 slots
-                while ((rows_more | (two_a - ns_a) | (two_b - ns_b) | (max(ns_a, ns_b) - 33)) >= 0) {      // (one sign test: rows left, slot counts within 33 .. limit)
+                while ((rows_more | (two_a - ns_a) | (two_b - ns_b) | (max(ns_a, ns_b) - 33) | wraps) >= 0) {      // (one sign test: rows left, slot counts within 33 .. limit)
                     DWS_ROW(~0ull, ns_a, ns_b, 2);
                     NJ = 2;
                     row_passes(2, ns_a, ns_b, rows_more, fast2{});
@@ -649,19 +720,20 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                     log_row(2, std::true_type{});
                     lin_l += row_bytes;
                     rows_more -= 1;
+                    wraps = ring_wraps();
                     __builtin_amdgcn_wave_barrier();
                 }
                 if (ended) break;
                 if (rows_more < 0 || ns_a > lim_a || ns_b > lim_b) break;
                 const int ns_max = max(ns_a, ns_b);
-                if (ns_max < 64) continue;                   // back to the two loops above
+                if (ns_max < 64 || wraps < 0) continue;      // back to the two loops above, by way of the relocation
                 // a half with 64 slots or more (0.01 % of the rows): the general form
                 NJ = (ns_max + 31) >> 5;
                 DWS_ROW(~0ull, ns_a, ns_b, NJ);
                 row_passes(NJ, ns_a, ns_b, rows_more, fast0{});
                 rows_more -= 1;
                 lin_l += row_bytes;
-                if ((ns_max & 31) == 0) ring_st(rbase, lin_l - 2u * sl - 2u, sepv);      // a half fills its last pass: no idle lane for the entry behind its row
+                if ((ns_max & 31) == 0) ring_st(lin_l - 2u * sl - 2u, sepv);      // a half fills its last pass: no idle lane for the entry behind its row
                 band_update(NJ, last_m0, last_mp, std::true_type{}, ns_a, ns_b);
                 log_row(NJ, std::true_type{});
                 if (ended) break;
@@ -678,12 +750,13 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 // compare it again)
                 const unsigned long long rmask = BALLOT(d < dlim) & BALLOT(nslot <= slot_lim);
                 if (rmask != inmask) break;
+                ring_relocate();      // (the half without a block too: its lanes store like the others, into a ring that nobody reads)
                 const int ns_max = max(ns_a, ns_b);
                 NJ = (ns_max + 31) >> 5;
                 DWS_ROW(rmask, ns_a, ns_b, NJ);
                 row_passes(NJ, ns_a, ns_b, no_count, std::integral_constant<int, 0>{});
                 lin_l += row_bytes;
-                if ((ns_max & 31) == 0) ring_st(rbase, lin_l - 2u * sl - 2u, sepv);
+                if ((ns_max & 31) == 0) ring_st(lin_l - 2u * sl - 2u, sepv);
                 band_update(NJ, last_m0, last_mp, std::false_type{}, ns_a, ns_b);
                 log_row(NJ, std::false_type{});
                 if (ended) break;
@@ -708,13 +781,13 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
             for (int j = 0; BALLOT(sl + 32 * j < en); ++j) {
                 const int k = emk_l + 64 * j, kk = k + k_offset;
                 if (sl + 32 * j < en) {
-                    const int x = ring_ld(rbase, rlin_l + 64u * (unsigned)j) >> 1;      // (base units: hkey has ten bits for it)
+                    const int x = ring_ld(rlin_l + 64u * (unsigned)j) >> 1;     // (base units: hkey has ten bits for it)
                     if (x >= q_len || x - k >= t_len) hkey = min(hkey, (kk << 10) | x);
                 }
             }
             hkey = half_min(hkey);
             if (inblock && hkey != 0x7fffffff) {
-                aligned = 1; end_k = (hkey >> 10) - k_offset; end_x = hkey & 1023; end_d = d;
+                end_k = (hkey >> 10) - k_offset; end_x = hkey & 1023; end_d = d;
                 end_mk = emk_l - 2 * sl;
                 dlim = 0;
             }
@@ -728,9 +801,9 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
         const bool fin = inblock && !row_ok;
 
         // ---- 4. tail traceback == trim_mismatch_end(.., 4, ..) (gapalign.cpp:47-68), for the halves whose rows just ended
-        bool has_aln = fin && aligned;
+        bool has_aln = fin && end_d >= 0;
         // rows ran without reaching an end: needs the best point (dw_extend).  CNS: Align has failed, the direction ends (dw.cpp:302-304)
-        bool handover = !CNS && fin && d > 0 && !aligned;
+        bool handover = !CNS && fin && d > 0 && end_d < 0;
         const int end_y = end_x - end_k;
         const int aln_size = (end_x + end_y + end_d) / 2;
         int cd = end_d, ck = end_k, cx2 = 2 * end_x;      // cx2, acnt2: the walk's x and its column count in doubled units, like the ring's entries
@@ -743,7 +816,10 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
         const unsigned int lin_u = lin_l - 2u * sl;
         unsigned int clin = rlin_l - 2u * sl;
         int cmin = end_mk;
-        int sepc = ~ring_ld(rbase, lin_u - 2u);
+        int sepc = ~ring_ld(lin_u - 2u);
+        // Rows from the origin up to lin_u are of the current lap; once the walk has gone through the link it is in the lap before, whose rows
+        // are whole while they lie ROW_STORE bytes or more ahead of lin_u (what the passes of the last row may have stored behind it).
+        bool crossed = false;
         while (BALLOT(tracing)) {
             if (tracing) {
                 // The path came to (cx2, diagonal ck) of row cd from diagonal ck - 1 (vl, one query base) or ck + 1 (vr, one target base)
@@ -753,19 +829,28 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 // tests (k == min_k: from the right; k == max_k: from the left) do: inside row cd - 1 but outside the band that row cd
                 // was cut to, the left neighbour of min_k has vl + 1 < vr and the right neighbour of max_k vr < vl + 1 (see row_passes).
                 // One straight line of selects (nested conditions cost a copy of every carried value per branch); in row 0 (cd == 0:
-                // the snake runs back to x = 0) the ring reads are made and not used — a ring address is always inside the ring.
+                // the snake runs back to x = 0), and in a step that finds the row lost, the ring reads are made and not used — LDS reads fault nowhere.
                 const bool up = cd > 0;
-                const int sp = ~ring_ld(rbase, clin - 2u);
+                const int sp = ~ring_ld(clin - 2u);      // (a relocated row: the copy at entry 2)
                 const int pcut = (sepc >> 8) & 127, pns = sp & 255;
-                const unsigned int plin = clin - 2u - 2u * (unsigned)pns;
-                // the row in front has left the ring (128: what the idle lanes of the last row's passes may have written behind it, see
-                // row_passes), or its cut was 127 or more and is not recorded: the unit is handed over, whatever else this step computes
-                const bool lost = up && (pcut == 127 || lin_u - plin > 2 * RCAP - 128);
+                // the row in front ends at the entry in front of this row, or, for a row at the ring's origin (never row 0: `up`), where the link says
+                const bool cross = (clin & (2u * RCAP - 1u)) == 2u * RING_ORG;
+                // (the link: the low bits of the word at the origin, read in every step rather than kept in a register across the walk)
+                const uint32_t link = *(lds_u32_t*)(uintptr_t)RING_BASE(clin) & (2u * RCAP - 1u);
+                const unsigned int plin = (cross ? RING_BASE(clin) | link : clin - 2u) - 2u * (unsigned)pns;
+                // the row in front has left the ring — it is in the lap before and the write point has come within ROW_STORE bytes of it (what the
+                // idle lanes of the last row's passes may have written behind it, see row_passes; that bound also keeps the walk from a second
+                // link: lin_u + ROW_STORE lies behind the origin) —, or its cut was 127 or more and is not recorded: the unit is handed over,
+                // whatever else this step computes
+                const bool over = crossed || cross;
+                const bool lost = up && (pcut == 127 || (over && (int)(plin - lin_u) < (int)ROW_STORE));
+                nev += (up && cross && sl == NEV_LINK) ? 1u : 0u;
+                crossed = over;
                 const int pmin = cmin - 2 * pcut + 1;
                 // byte offsets of the two neighbours in row cd - 1 (two bytes per diagonal, diagonals two apart): one unsigned compare
                 // each against the row's last offset
                 const unsigned int ol = (unsigned)(ck - 1 - pmin), olast = 2u * (unsigned)pns - 2u;
-                const int rl = ring_ld(rbase, plin + ol), rr = ring_ld(rbase, plin + ol + 2u);
+                const int rl = ring_ld(plin + ol), rr = ring_ld<2>(plin + ol);
                 const int vl = ol <= olast ? rl : -2, vr = ol + 2u <= olast ? rr : -2;      // (-1 in doubled units)
                 const int x1 = up ? max(vl + 2, vr) : 0;
                 const int sn = cx2 - x1;
@@ -803,11 +888,11 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                     ca.hand_units[1u + atomicAdd(ca.hand_units, 1u)] = unit;
                     CnsDir D = {0, 0, 0, 0, 0, -1};
                     ca.dres[unit] = D;
-                    nhand += 1;
+                    nev += 1;
                 }
             } else {
-                nblocks += (sl == 0) ? 1u : 0u;
-                cells += (sl == 0) ? ((lin_l - 6u) >> 1) - (unsigned)d : 0u;
+                nev += (sl == NEV_BLOCKS) ? 1u : 0u;
+                nev += (sl == NEV_CELLS) ? ((lin_l - org_l - 6u) >> 1) + (*(lds_u32_t*)(uintptr_t)RING_BASE(wrap_l) >> RING_LINK_BITS) - (unsigned)d : 0u;
                 bool keep = has_aln && (last_block || found);
                 const int kept_q = end_x - qcnt, kept_t = end_y - tcnt, kept_cols = aln_size - acnt;      // (last block: nothing was walked)
                 keep = keep && kept_q != 0;
@@ -820,7 +905,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                         ca.hand_units[1u + atomicAdd(ca.hand_units, 1u)] = unit;
                         CnsDir D = {0, 0, 0, 0, 0, -1};
                         ca.dres[unit] = D;
-                        nhand += 1;
+                        nev += 1;
                     }
                 } else {
                     if (keep) {
@@ -848,12 +933,13 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                     h.unit = unit; h.qidx = qidx; h.tidx = tidx;
                     h.R.qbases = Rq; h.R.tbases = Rt; h.R.matches = Rm; h.R.columns = Rc; h.R.blocks = Rb; h.R.pad = 0;
                     hand[atomicAdd(hand_count, 1u)] = h;
-                    nhand += 1;
+                    nev += 1;
                 }
                 need_unit = true;
             } else {
-                nblocks += (sl == 0) ? 1u : 0u;
-                cells += (sl == 0) ? ((lin_l - 6u) >> 1) - (unsigned)d : 0u;      // diagonals visited in this block (d rows, one -1 behind each)
+                nev += (sl == NEV_BLOCKS) ? 1u : 0u;
+                // diagonals visited in this block (d rows, one -1 behind each): the entries from row 0 to lin, with those the relocations skipped
+                nev += (sl == NEV_CELLS) ? ((lin_l - org_l - 6u) >> 1) + (*(lds_u32_t*)(uintptr_t)RING_BASE(wrap_l) >> RING_LINK_BITS) - (unsigned)d : 0u;
                 Rb += 1;
                 stop = !has_aln || !trim_ok;
                 if (!stop) {
@@ -879,12 +965,15 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
         DWS_T(t_f);
         DWS_ADD(tk_acct, t_e, t_f);
     }
-    unsigned long long c64 = cells, b64 = nblocks, h64 = nhand;
-    for (int off = 32; off > 0; off >>= 1) { b64 += __shfl_xor(b64, off); c64 += __shfl_xor(c64, off); h64 += __shfl_xor(h64, off); }
+    unsigned long long c64 = sl == NEV_CELLS ? nev : 0u, b64 = sl == NEV_BLOCKS ? nev : 0u;
+    unsigned long long h64 = sl == NEV_HAND ? nev : 0u, r64 = sl == NEV_RELOC ? nev : 0u, l64 = sl == NEV_LINK ? nev : 0u;
+    for (int off = 32; off > 0; off >>= 1) { b64 += __shfl_xor(b64, off); c64 += __shfl_xor(c64, off); h64 += __shfl_xor(h64, off); r64 += __shfl_xor(r64, off); l64 += __shfl_xor(l64, off); }
     if (lane == 0) {
         atomicAdd(&counters[3], b64);
         atomicAdd(&counters[4], c64);
         atomicAdd(&counters[8], h64);          // units handed over
+        atomicAdd(&counters[30], r64);         // rows relocated to the ring's origin
+        atomicAdd(&counters[31], l64);         // tail-walk steps taken through a link
 #ifdef MECAT_DW_STATS
         atomicAdd(&counters[9], nrows);          // dual rows
         atomicAdd(&counters[10], nidle);         // dual rows with one idle half

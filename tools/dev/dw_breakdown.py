@@ -39,6 +39,9 @@ print("dual rows with one idle half %.1f %%, with a second pass %.1f %%, with th
 n_one, n_one32 = D[28], D[29]
 print("dual rows with both halves in a block and at most 32 slots in each: %d, %.2f %% of them with a half at exactly 32 slots" % (n_one, 100.0 * n_one32 / max(1, n_one)))
 ur = sum(nh)
+n_reloc, n_link = D[30], D[31]
+print("rows relocated to the ring's origin: %d, one in %.1f unit rows (%.2f %%); tail-walk steps taken through a link: %d; units handed over: %d"
+      % (n_reloc, ur / max(1, n_reloc), 100.0 * n_reloc / max(1, ur), n_link, D[8]))
 print()
 print("| band width of a unit row | <= 8 | <= 16 | <= 24 | <= 32 | <= 48 | <= 64 | <= 96 | more |")
 print("|---|---|---|---|---|---|---|---|---|")
