@@ -296,6 +296,31 @@ int  mhip_asm_extend_run(mhip_ctx* ctx, const mhip_volume* block, const mhip_vol
                          int64_t* total_words);
 int  mhip_asm_extend_fetch(mhip_ctx* ctx, int n, int32_t* dirs /*[2 n][6]*/, uint64_t* word_offs /*[2 n + 1]*/, uint32_t* ops_dense /*[total_words]*/);
 
+/* ---- mecat2ref, the reads-to-reference mapper, stage 1: seeding and candidate selection ----
+ * Replaces the part of reference_mapping in front of its extend_candidate loop (mecat2ref/mecat2ref_impl_large.cpp:351-561 for the first
+ * round, :619-825 for the second, with transnum_buchang :64-90, insert_loc :92-130 and find_location, mecat2ref_aux.cpp:6-83): both
+ * strands of query reads [rid_begin, rid_end) of `reads` against the reference volume `ref` (mecat_amd/host/ref_genome.h makes it from
+ * the FASTA file) whose table is mhip_index_build's (creat_ref_index :133-271 with sumvalue_x :53-62: k = 13, cap 128).  A query k-mer
+ * that holds a letter other than upper-case A, C, G, T is skipped (atcttrans :44-51; the tool does not upper-case reads): `reads` carries
+ * an N plane (mhip_volume_set_nplane) that is 3 at every such letter.  Every read starts from untouched segments (:605-616).
+ * out[(rid - rid_begin) * maxc ..] = the read's candidates in list order (forward strand first, stable by descending score, at most
+ * maxc), out_counts[] their number.  Positions are the tool's: loc1 the 1-based start of the seed 13-mer in the concatenated reference,
+ * loc2 the 0-based start in the mapped strand of the read.  Refused with a message: a read of 100 000 letters or more (RM, the tool's
+ * buffers).  A read shorter than 13 letters has no candidates (the tool reads past the string there). */
+typedef struct { int64_t loc1, loc2, left1, left2, right1, right2; int32_t score, num1, num2, chain; } mhip_ref_candidate; /* candidate_save, mecat2ref_defs.h:88-93; chain 0 = 'F', 1 = 'R' */
+typedef struct { int32_t maxc; int32_t round; double ddfs_cutoff; } mhip_ref_seed_params;  /* round 0: ZV 1000, BC by length, gate 6; 1: ZVS 2000, BC 5, gate 4 */
+/* maxc 10 (kDefaultNumCandidates, mecat2ref.cpp:18), round 0, cutoff 0.25 for BOTH technologies: mecat2ref_impl_large.cpp:13-15 names
+ * 0.1 for nanopore and never assigns it, so the tool maps nanopore reads at 0.25 too (a caller may still set 0.1) */
+void mhip_ref_seed_params_default(mhip_ref_seed_params* p, int tech);
+int  mhip_ref_seed_reads(mhip_ctx* ctx, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end,
+                         const mhip_ref_seed_params* params, mhip_ref_candidate* out /*[n][maxc]*/, int32_t* out_counts);
+/* the same with DEVICE pointers for out / out_counts (the lists stay in HBM for the extension stage) */
+int  mhip_ref_seed_reads_dev(mhip_ctx* ctx, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end,
+                             const mhip_ref_seed_params* params, mhip_ref_candidate* d_out, int32_t* d_out_counts);
+/* measurement hook: of the last mhip_ref_seed_reads* call — [0] reads, [1] reads redone with full record pools, [2] resident waves,
+ * [3] records per pool */
+void mhip_ref_seed_stats(int64_t out[4]);
+
 /* mhip_index_build by all ranks of the communicator together (replaces create_ref_index, common/lookup_table.cpp:63-160, in a
  * multi-GPU cell): the 4^13 key space is cut into P contiguous ranges of equal occupancy, each rank builds the buckets of its range,
  * positions and table slices are all-gathered (counts first, then payload), and every rank returns the complete table — equal, array

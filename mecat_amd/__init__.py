@@ -6,7 +6,9 @@ the multi-GPU launcher; it contains no compute and has NO CPU fallback: importin
 shared library is missing, and every call raises MhipError if no gfx950 device is usable.
 """
 from .hip import (  # noqa: F401
-    Candidate, AlnJob, AlnResult, Context, Index, MhipError, Params, Volume, lib, lib_path,
+    Candidate, AlnJob, AlnResult, Context, Index, MhipError, Params, RefCandidate, RefSeedParams, Volume, lib, lib_path, ref_seed_params,
+    ref_seed_reads,
 )
 
-__all__ = ["Candidate", "AlnJob", "AlnResult", "Context", "Index", "MhipError", "Params", "Volume", "lib", "lib_path"]
+__all__ = ["Candidate", "AlnJob", "AlnResult", "Context", "Index", "MhipError", "Params", "RefCandidate", "RefSeedParams", "Volume", "lib",
+           "lib_path", "ref_seed_params", "ref_seed_reads"]

@@ -343,6 +343,57 @@ def volume_set_nplane(ctx, vol, nplane):
     _chk(lib().mhip_volume_set_nplane(ctx.h, vol.h, nplane.ctypes.data if nplane is not None else None))
 
 
+class RefCandidate(C.Structure):
+    """mhip_ref_candidate (candidate_save, mecat2ref/mecat2ref_defs.h:88-93)"""
+    _fields_ = [(n, C.c_int64) for n in ("loc1", "loc2", "left1", "left2", "right1", "right2")] + [(n, C.c_int32) for n in ("score", "num1", "num2", "chain")]
+
+
+class RefSeedParams(C.Structure):      # mhip_ref_seed_params
+    _fields_ = [("maxc", C.c_int32), ("round", C.c_int32), ("ddfs_cutoff", C.c_double)]
+
+
+REF_CAND_DTYPE = np.dtype([(n, np.int64 if t is C.c_int64 else np.int32) for n, t in RefCandidate._fields_])
+assert REF_CAND_DTYPE.itemsize == C.sizeof(RefCandidate) == 64 and C.sizeof(RefSeedParams) == 16
+
+
+def ref_seed_params(tech=0, **kw):
+    """mhip_ref_seed_params_default, then the given members"""
+    p = RefSeedParams()
+    lib().mhip_ref_seed_params_default.argtypes = [C.POINTER(RefSeedParams), C.c_int]
+    lib().mhip_ref_seed_params_default.restype = None
+    lib().mhip_ref_seed_params_default(C.byref(p), tech)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+_REF_SEED_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(RefSeedParams), C.c_void_p, C.c_void_p]
+
+
+def ref_seed_reads(ctx, idx, ref, reads, rid_begin, rid_end, params):
+    """mhip_ref_seed_reads: mecat2ref's seeding and candidate selection -> (cands [n, maxc] REF_CAND_DTYPE, counts int32[n])"""
+    n = max(rid_end - rid_begin, 0)
+    out = np.zeros((n, max(params.maxc, 1)), dtype=REF_CAND_DTYPE)
+    cnt = np.zeros(n, dtype=np.int32)
+    lib().mhip_ref_seed_reads.argtypes = _REF_SEED_ARGS
+    _chk(lib().mhip_ref_seed_reads(ctx.h, idx.h, ref.h, reads.h, rid_begin, rid_end, C.byref(params), out.ctypes.data, cnt.ctypes.data))
+    return out, cnt
+
+
+def ref_seed_reads_dev(ctx, idx, ref, reads, rid_begin, rid_end, params, d_out, d_counts):
+    """mhip_ref_seed_reads_dev: the same into device buffers (e.g. of mhip_ctx_buffer)"""
+    lib().mhip_ref_seed_reads_dev.argtypes = _REF_SEED_ARGS
+    _chk(lib().mhip_ref_seed_reads_dev(ctx.h, idx.h, ref.h, reads.h, rid_begin, rid_end, C.byref(params), d_out, d_counts))
+
+
+def ref_seed_stats():
+    """mhip_ref_seed_stats of the last call: dict(reads, redone, waves, pool)"""
+    v = (C.c_int64 * 4)()
+    lib().mhip_ref_seed_stats.restype = None
+    lib().mhip_ref_seed_stats(v)
+    return dict(reads=int(v[0]), redone=int(v[1]), waves=int(v[2]), pool=int(v[3]))
+
+
 def asm_jobs_from_candidates(cands, counts, rid_begin=0):
     """the (candidate, both directions) jobs of an asm_seed_reads table, read by read in list order (include/mecat_hip.h: x0 = loc1 - 1 -
     readstart; left from (x0 + 12, loc2 + 12) with left1 / left2 bases, right from (x0, loc2) with right1 / right2) -> [n] ASM_JOB_DTYPE"""
