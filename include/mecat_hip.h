@@ -321,6 +321,34 @@ int  mhip_ref_seed_reads_dev(mhip_ctx* ctx, const mhip_index* idx, const mhip_vo
  * [3] records per pool */
 void mhip_ref_seed_stats(int64_t out[4]);
 
+/* ---- mecat2ref, stage 2: every listed candidate through DiffAligner::go, with the aligned strings (PacBio mode) ----
+ * Replaces the extend_candidate loop of reference_mapping (mecat2ref/mecat2ref_impl_large.cpp:566-582 for round 1, :829-845 for round 2)
+ * with extend_candidate (mecat2ref_aux.cpp:123-183), extract_sequences (:85-121) and DiffAligner::go (common/diff_gapalign.cpp:294-349;
+ * blocks, band, best-point fallback, tail anchor and traceback :39-292, common/gapalign.cpp:9-68).  cands / counts are
+ * mhip_ref_seed_reads' output for the same reads [rid_begin, rid_end) and maxc; slot (read, k) of the result is slot (read, k) of the list,
+ * which is the tool's call order.  The target of a candidate is the window [loc1 - 1 - left_ref_size, loc1 - 1 + right_ref_size) of the
+ * concatenated reference (`ref`: mecat_amd/host/ref_genome.h), the query the read on the candidate's strand.  The strand is the tool's:
+ * the whole read reversed, only upper-case A, C, G, T complemented (:376-410) — `reads` must be packed by mecat_amd/host/ref_reads.h
+ * (lower-case a, c, g, t keep their codes, N plane 3 there and at every other letter; the plane is what keeps a base from being
+ * complemented).  A result: ok = columns >= 1000 (the tool keeps only those), chain / vscore of the candidate, qb / qe / qs and sb / se as
+ * extend_candidate stores them (:158-162), cols = the length of the aligned strings.  The strings are 2-bit columns in string order,
+ * 16 per word from the low end: 0 = both bases, 1 = target base only ('-' in the query string), 2 = query base only
+ * (mecat_amd/host/ref_results.h rebuilds the text).  Empty slots and results with ok = 0 take zero words.
+ * mhip_ref_extend_run extends the batch, leaves everything on the device and returns the words the ok results take;
+ * mhip_ref_extend_fetch — same context, before the next _run — copies out res[n * maxc], word_offs[n * maxc + 1] (result s occupies words
+ * [word_offs[s], word_offs[s + 1]) of ops_dense) and the words.  Refused with a message (-1): tech != 0 (nanopore mode needs the X-drop
+ * aligner's strings, not built), a read of 100 000 letters or more (RM), a candidate whose loc1 or loc2 lies outside the reference or
+ * the read (nothing is extended then). */
+typedef struct { int32_t ok, chain, vscore, qb, qe, qs; int64_t sb, se; int32_t cols, pad; } mhip_ref_result;   /* TempResult without its strings, mecat2ref_defs.h */
+int  mhip_ref_extend_run(mhip_ctx* ctx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, int maxc, int tech,
+                         const mhip_ref_candidate* cands /*[n][maxc]*/, const int32_t* counts, int64_t* total_words);
+/* the same with DEVICE lists: mhip_ref_seed_reads_dev's output, nothing copied back in between */
+int  mhip_ref_extend_run_dev(mhip_ctx* ctx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, int maxc, int tech,
+                             const mhip_ref_candidate* d_cands, const int32_t* d_counts, int64_t* total_words);
+int  mhip_ref_extend_fetch(mhip_ctx* ctx, mhip_ref_result* res /*[n][maxc]*/, uint64_t* word_offs /*[n * maxc + 1]*/, uint32_t* ops_dense /*[total_words]*/);
+/* measurement hook: of the last mhip_ref_extend_run* call — [0] slots, [1] slices, [2] bytes of row scratch, [3] words of the column store */
+void mhip_ref_extend_stats(int64_t out[4]);
+
 /* mhip_index_build by all ranks of the communicator together (replaces create_ref_index, common/lookup_table.cpp:63-160, in a
  * multi-GPU cell): the 4^13 key space is cut into P contiguous ranges of equal occupancy, each rank builds the buckets of its range,
  * positions and table slices are all-gathered (counts first, then payload), and every rank returns the complete table — equal, array

@@ -7,8 +7,8 @@ shared library is missing, and every call raises MhipError if no gfx950 device i
 """
 from .hip import (  # noqa: F401
     Candidate, AlnJob, AlnResult, Context, Index, MhipError, Params, RefCandidate, RefSeedParams, Volume, lib, lib_path, ref_seed_params,
-    ref_seed_reads,
+    ref_extend, ref_seed_reads,
 )
 
 __all__ = ["Candidate", "AlnJob", "AlnResult", "Context", "Index", "MhipError", "Params", "RefCandidate", "RefSeedParams", "Volume", "lib",
-           "lib_path", "ref_seed_params", "ref_seed_reads"]
+           "lib_path", "ref_extend", "ref_seed_params", "ref_seed_reads"]

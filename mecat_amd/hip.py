@@ -394,6 +394,60 @@ def ref_seed_stats():
     return dict(reads=int(v[0]), redone=int(v[1]), waves=int(v[2]), pool=int(v[3]))
 
 
+class RefResult(C.Structure):
+    """mhip_ref_result: a TempResult (mecat2ref/output.h) without its strings"""
+    _fields_ = [(n, C.c_int32) for n in ("ok", "chain", "vscore", "qb", "qe", "qs")] + [("sb", C.c_int64), ("se", C.c_int64), ("cols", C.c_int32), ("pad", C.c_int32)]
+
+
+REF_RESULT_DTYPE = np.dtype([(n, np.int64 if t is C.c_int64 else np.int32) for n, t in RefResult._fields_])
+assert REF_RESULT_DTYPE.itemsize == C.sizeof(RefResult) == 48
+
+_REF_EXT_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+
+
+def ref_extend_run(ctx, ref, reads, rid_begin, rid_end, maxc, cands, counts, tech=0):
+    """mhip_ref_extend_run: mecat2ref's extension of the listed candidates (host lists, ref_seed_reads' layout) -> total words"""
+    cands = np.ascontiguousarray(cands, dtype=REF_CAND_DTYPE)
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    assert cands.size == max(rid_end - rid_begin, 0) * maxc and len(counts) == max(rid_end - rid_begin, 0)
+    tot = C.c_int64()
+    lib().mhip_ref_extend_run.argtypes = _REF_EXT_ARGS
+    _chk(lib().mhip_ref_extend_run(ctx.h, ref.h, reads.h, rid_begin, rid_end, maxc, tech, cands.ctypes.data, counts.ctypes.data, C.byref(tot)))
+    return tot.value
+
+
+def ref_extend_run_dev(ctx, ref, reads, rid_begin, rid_end, maxc, d_cands, d_counts, tech=0):
+    """mhip_ref_extend_run_dev: the same on device lists (mhip_ref_seed_reads_dev's output) -> total words"""
+    tot = C.c_int64()
+    lib().mhip_ref_extend_run_dev.argtypes = _REF_EXT_ARGS
+    _chk(lib().mhip_ref_extend_run_dev(ctx.h, ref.h, reads.h, rid_begin, rid_end, maxc, tech, d_cands, d_counts, C.byref(tot)))
+    return tot.value
+
+
+def ref_extend_fetch(ctx, n, maxc, total_words):
+    """mhip_ref_extend_fetch -> (res [n, maxc] REF_RESULT_DTYPE, word_offs uint64[n * maxc + 1], words uint32[total_words])"""
+    res = np.zeros((n, maxc), dtype=REF_RESULT_DTYPE)
+    offs = np.zeros(n * maxc + 1, dtype=np.uint64)
+    words = np.zeros(max(total_words, 1), dtype=np.uint32)
+    lib().mhip_ref_extend_fetch.argtypes = [C.c_void_p] * 4
+    _chk(lib().mhip_ref_extend_fetch(ctx.h, res.ctypes.data, offs.ctypes.data, words.ctypes.data))
+    return res, offs, words[:total_words]
+
+
+def ref_extend(ctx, ref, reads, rid_begin, rid_end, maxc, cands, counts, tech=0):
+    """run + fetch -> (res, word_offs, words)"""
+    tot = ref_extend_run(ctx, ref, reads, rid_begin, rid_end, maxc, cands, counts, tech)
+    return ref_extend_fetch(ctx, max(rid_end - rid_begin, 0), maxc, tot)
+
+
+def ref_extend_stats():
+    """mhip_ref_extend_stats of the last run: dict(slots, slices, row_bytes, store_words)"""
+    v = (C.c_int64 * 4)()
+    lib().mhip_ref_extend_stats.restype = None
+    lib().mhip_ref_extend_stats(v)
+    return dict(slots=int(v[0]), slices=int(v[1]), row_bytes=int(v[2]), store_words=int(v[3]))
+
+
 def asm_jobs_from_candidates(cands, counts, rid_begin=0):
     """the (candidate, both directions) jobs of an asm_seed_reads table, read by read in list order (include/mecat_hip.h: x0 = loc1 - 1 -
     readstart; left from (x0 + 12, loc2 + 12) with left1 / left2 bases, right from (x0, loc2) with right1 / right2) -> [n] ASM_JOB_DTYPE"""
