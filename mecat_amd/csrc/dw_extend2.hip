@@ -31,10 +31,13 @@
 // The scalar side of a row is kept as short as its vector side (the kernel ran at 78 % of the device's scalar issue rate,
 // profiles/dw_scalar_side.md): a two-pass row takes the lane masks of both passes from one s_bfm_b64 per half (pass_bits), and the band
 // update puts its 64-bit words together by moves (pair64) and takes a half's slot count from one sum.
+// A one-pass row has no test for the half that fills all of its 32 lanes (10.85 % of those rows), where no idle lane stores the entry behind
+// the row: every lane stores that entry one slot to its right in front of its own store, two scalar instructions and a branch per row
+// for one LDS store (row_passes; profiles/dw_row_exits.md).
 // 64 VGPRs, 19 KB of LDS per four waves, eight waves per SIMD (tests/test_dw_resources_cpu.py holds the compiler to it); on its common
-// path a one-pass dual row is 40 VALU (120 issue cycles) + 27 SALU, a two-pass row 62 (188) + 35 (tests/test_dw_ring_linear_cpu.py
-// caps the cycles, counting the rare part of the snake step too: 124 / 196; tests/test_dw_row_scalar_cpu.py the scalar instructions, 33 /
-// 47 as listed); VALU-issue bound (profiles/r03_dw_row_breakdown.md, r05_dw_attempt.md).  The code between two row loops is 10 % of a wave's life (profiles/dw_block_setup.md).  What is and is not
+// path a one-pass dual row is 40 VALU (120 issue cycles) + 25 SALU, a two-pass row 62 (188) + 35 (tests/test_dw_ring_linear_cpu.py
+// caps the cycles, counting the rare part of the snake step too: 124 / 196; the scalar instructions as listed are 31 / 47:
+// tests/test_dw_row_exits_cpu.py caps the one-pass row's, tests/test_dw_row_scalar_cpu.py the two-pass row's); VALU-issue bound (profiles/r03_dw_row_breakdown.md, r05_dw_attempt.md).  The code between two row loops is 10 % of a wave's life (profiles/dw_block_setup.md).  What is and is not
 // settled about the row loops: DESIGN.md §6.
 #include <stdio.h>
 #include <stdlib.h>
@@ -498,7 +501,8 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
         // bookkeeping fold away).  ns_a / ns_b: the two halves' slot counts on the scalar unit.  A row is followed in the ring by one
         // negative entry (sepv), which the first idle lane of the last pass writes: every lane of a pass stores (its x, or sepv when idle) at
         // its own position — no exec juggling around the store, no store of its own for that entry (unless a half fills its last pass to the
-        // last lane: the caller's business, see `full` below).  What idle lanes write beyond it is overwritten by the rows that
+        // last lane: FAST 1 stores the entry for that case on every row, see the store below; behind a general row it is the caller's
+        // business).  What idle lanes write beyond it is overwritten by the rows that
         // follow, except for up to 64 entries behind the last row of a block with NJ <= 2: the tail traceback's window is shortened
         // by as much (rows with more passes guard their stores).  FAST 1: 1 <= slots <= 32 in both halves, one pass; FAST 2: 1 <= slots
         // <= 63, two passes; FAST 0: anything.  rows_more: the caller's count-down of rows, which a pass marks — and `ended` gets the
@@ -597,6 +601,15 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 // one select per pass: the ring takes the low 16 bits of v, and an idle lane's m0 = sepv + y is about -2^29 (sep_word; its
                 // y is within +-2^17: x from 16 bits of the ring plus its snake, k2 a diagonal of the block)
                 const int v = act ? x : sepv;
+                // FAST 1: the entry behind a half's row of exactly 32 slots, which no idle lane of its stores, without a test for it: every
+                // lane stores sepv one slot to its right first (lane i at slot i + 1), then its own value at its own slot.  The LDS
+                // instructions of a wave are performed in program order, so slots 1 .. 31 end up with what their own lanes put there, as
+                // without the first store, and slot 32 holds sepv: the entry behind a 32-slot row; behind a narrower one, one more of what
+                // its idle lanes leave there anyway, inside ROW_STORE.  (sepv still describes this row: the band update comes later.)
+                // An asm statement: as ring_st<2> the compiler merges a lane's two stores into one ds_write_b32, in which lanes i and i + 1
+                // write slot i + 1 in the same instruction and the order that lets x win is gone
+                // (tests/test_gpu_dw_row_exits.py, tests/test_dw_row_exits_cpu.py).
+                if (FAST == 1) asm volatile("ds_write_b16 %0, %1 offset:2" : : "v"(lin_l), "v"(sepv) : "memory");
                 if (NJ <= 2 || tt <= nslot) ring_st(lin_l + 64u * (unsigned)j, v);
                 mp = m0;
                 m0 = v + y;                         // also read by the band update (NJ <= 2); idle lanes never qualify
@@ -694,14 +707,11 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 // halves are relocated and the loops are entered again.
                 ring_relocate();
                 int wraps = 0;
-                // one-pass rows (rows left, and both slot counts within their limits: one sign test; why the `full` test stays in the
-                // loop: profiles/dw_scalar_side.md, S3)
+                // one-pass rows (rows left, and both slot counts within their limits: one sign test)
                 while ((rows_more | (one_a - ns_a) | (one_b - ns_b) | wraps) >= 0) {
                     DWS_ROW(~0ull, ns_a, ns_b, 1);
-                    const bool full = ((ns_a | ns_b) & 32) != 0;       // a half has all of its 32 lanes on diagonals: nobody stores the entry
-                    row_passes(1, ns_a, ns_b, rows_more, fast1{});     //   behind its row (the other half's idle lane rewrites its own)
+                    row_passes(1, ns_a, ns_b, rows_more, fast1{});     // (stores the entry behind a row of 32 slots itself)
                     lin_l += row_bytes;
-                    if (full) ring_st(lin_l - 2u * sl - 2u, sepv);
                     band_update(1, last_m0, last_mp, std::true_type{}, ns_a, ns_b);
                     log_row(1, std::true_type{});
                     // (a row that reached an end leaves the loop through its bound, which snake_step_end has marked: a second exit makes
