@@ -34,10 +34,15 @@
 // A one-pass row has no test for the half that fills all of its 32 lanes (10.85 % of those rows), where no idle lane stores the entry behind
 // the row: every lane stores that entry one slot to its right in front of its own store, two scalar instructions and a branch per row
 // for one LDS store (row_passes; profiles/dw_row_exits.md).
+// The snake step takes its minimum in 16 bits (v_min_u16, which issues at the plain-add rate), pass 2 forms its y with two plain adds and
+// no register for the negated diagonal, and a two-pass row requests pass 2's two entries of the row in front right behind pass 1's, so that
+// their LDS round trip runs under pass 1's snake instead of behind it (profiles/dw_row_latency.md).
 // 64 VGPRs, 19 KB of LDS per four waves, eight waves per SIMD (tests/test_dw_resources_cpu.py holds the compiler to it); on its common
-// path a one-pass dual row is 40 VALU (120 issue cycles) + 25 SALU, a two-pass row 62 (188) + 35 (tests/test_dw_ring_linear_cpu.py
-// caps the cycles, counting the rare part of the snake step too: 124 / 196; the scalar instructions as listed are 31 / 47:
-// tests/test_dw_row_exits_cpu.py caps the one-pass row's, tests/test_dw_row_scalar_cpu.py the two-pass row's); VALU-issue bound (profiles/r03_dw_row_breakdown.md, r05_dw_attempt.md).  The code between two row loops is 10 % of a wave's life (profiles/dw_block_setup.md).  What is and is not
+// path a one-pass dual row is 40 VALU (118 issue cycles) + 25 SALU, a two-pass row 62 (182) + 35 (tests/test_dw_row_latency_cpu.py
+// caps the cycles, counting the rare part of the snake step too: 122 / 190; the scalar instructions as listed are 31 / 47:
+// tests/test_dw_row_exits_cpu.py caps the one-pass row's, tests/test_dw_row_scalar_cpu.py the two-pass row's).  About 70 % issue-bound and
+// 30 % latency-bound by its time at 32, 28 and 24 waves per CU (profiles/dw_row_latency.md; earlier: profiles/r03_dw_row_breakdown.md,
+// r05_dw_attempt.md).  The code between two row loops is 10 % of a wave's life (profiles/dw_block_setup.md).  What is and is not
 // settled about the row loops: DESIGN.md §6.
 #include <stdio.h>
 #include <stdlib.h>
@@ -229,10 +234,6 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
     // relocated to the ring's origin, lane 2 the tail-walk steps taken through a link, lane 3 the blocks, lane 4 the cells (one register
     // across the row loops where each count had its own); summed per kind at the kernel's end
     unsigned int nev = 0;
-    // -128, pass 2's share of y = x - (mk_l + 128), as the result of an asm statement: the compiler then keeps it in a scalar register for the
-    // kernel's life — a plain constant it sets up again inside the two-pass loop, one scalar instruction per row
-    int pass2_k;
-    asm("s_movk_i32 %0, 0xff80" : "=s"(pass2_k));
     enum { NEV_HAND = 0, NEV_RELOC = 1, NEV_LINK = 2, NEV_BLOCKS = 3, NEV_CELLS = 4 };
 #ifdef MECAT_DW_STATS
     // development build only (tools/dev/dw_breakdown.sh -> profiles/rNN_dw_row_breakdown.md): where the wave's time and rows go.
@@ -523,6 +524,7 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 two_m1 = pair64(word_lo(ma), word_lo(mb));
                 two_m2 = pair64(word_hi(ma), word_hi(mb));
             }
+            int vl2 = 0, vr2 = 0;               // FAST 2: pass 2's two entries of the row in front, requested next to pass 1's
             int j = 0;
             do {                                 // at least one pass (a pass over an empty band only moves idle lanes)
                 const int tt = sl + 32 * j;
@@ -539,7 +541,18 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 const bool act = __builtin_amdgcn_inverse_ballot_w64(amask);
                 const int k2 = mk_l + 128 * j;                          // (doubled: lane offset 4 sl, 128 per pass)
                 const unsigned int rp = pb_l + 64u * (unsigned)j;       // idle lanes read (and ignore) whatever the ring holds there
-                const int vl = ring_ld(rp), vr = ring_ld<2>(rp);
+                const int vl = (FAST == 2 && j == 1) ? vl2 : ring_ld(rp), vr = (FAST == 2 && j == 1) ? vr2 : ring_ld<2>(rp);
+                // FAST 2: pass 2's reads are requested here, right behind pass 1's, where they used to follow pass 1's snake and store with
+                // a whole LDS round trip in the row's serial chain and nothing to overlap it (profiles/dw_row_latency.md).  The row they
+                // read is the one in front, at pb_l as before: no store of this row's pass 1 lands in it (an active lane of pass 2 reads
+                // at most the entry behind that row; this row starts behind that entry, or at the ring's origin).
+                // An asm statement: written as ring_ld<64>(pb_l) up here, the compiler leaves the sign extension behind the snake loop
+                // (ds_read_u16 + v_bfe_i32: two more instructions per row).  It therefore does not know that the two results are in
+                // flight and inserts no wait for them.  None is needed: LDS returns in order and these two stand right behind pass 1's
+                // two reads (the "memory" clobber keeps them there), so the wait in front of pass 1's v_max_i16 below, which takes vr,
+                // covers them — and pass 2 comes behind pass 1's snake.  tests/test_dw_row_latency_cpu.py holds the listing to it: the four
+                // reads in this order, a wait between them and that v_max_i16, and no instruction in between that names vl2 or vr2.
+                if (FAST == 2 && j == 0) asm volatile("ds_read_i16 %0, %2 offset:64\n\tds_read_i16 %1, %2 offset:66" : "=&v"(vl2), "=&v"(vr2) : "v"(pb_l) : "memory");
                 // :138-142 `if (k == min_k || (k != max_k && V[k-1] < V[k+1])) x = V[k+1]; else x = V[k-1] + 1;` as max(vl + 1, vr), in
                 // doubled units max(vl + 2, vr): inside the band the two are the same thing (vl < vr <=> vr >= vl + 1).  At k == min_k the
                 // entry on the left is either the entry between two rows — ~(nslot | cut << 8) with nslot >= 1, hence <= -2: vl + 2 <= 0 <=
@@ -577,7 +590,16 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                 // that value + y, about -2^29 on an idle lane (so neither the row maximum nor the band update sees them), snake_step_end masks the lanes at
                 // their limit with amask — an idle lane neither asks for a further step nor ends a block —, and the CNS flag bits are
                 // masked by the reader with the row's slot count.  Nothing behind the passes reads a lane's x, y, limc or nn.
-                int y = (FAST == 2 && j == 1) ? (x - mk_l) + pass2_k : x - k2;
+                // y = x - k2.  FAST 2, pass 2 (k2 = mk_l + 128): x - mk_l, then the literal -128 — two plain adds, as asm statements: left to
+                // itself the compiler keeps -mk_l in a register of its own (one v_sub_u32 per row) and a scalar register for the constant, and
+                // forms y with a v_add3_u32 that takes that scalar operand (profiles/dw_row_latency.md)
+                int y;
+                if (FAST == 2 && j == 1) {
+                    asm("v_sub_u32 %0, %1, %2" : "=v"(y) : "v"(x), "v"(mk_l));
+                    asm("v_add_u32 %0, 0xffffff80, %0" : "+v"(y));
+                } else {
+                    y = x - k2;
+                }
 #ifdef MECAT_DW_STATS
                 snake2 -= 1;
 #endif
@@ -592,11 +614,16 @@ __global__ __launch_bounds__(AL_BLOCK, CNS ? CNS_FWD_WAVES_PER_SIMD : DW2_WAVES_
                     // 0..15 equal bases (doubled: 0..30), or >= 16 (0x7ffffffe) when the whole window matches.  A lane with exactly 16
                     // bases left that all match asks for one more step, which then moves nothing.
                     const int m = match16_le2<STAGED_T_BYTES>(ubase, x, y);
-                    const int nn = min(m, limc);
-                    // one compare per step: nn == limc holds exactly on the lanes that go on (limc == 32) or have nothing left of the
-                    // query or of the target on their diagonal (limc < 32); which of the two is looked at only when an active lane has it
+                    // nn = min(m, limc) in 16 bits, which issues at the plain-add rate where v_min_i32 takes twice as long: on a live lane
+                    // limc is 0 .. 32 and m 0 .. 30 or 0x7ffffffe, whose low half 0xfffe is still above any limc; the result comes back
+                    // zero-extended.  (An idle lane's limc may be anything: nothing of its nn is kept.)
+                    int nn;
+                    asm("v_min_u16 %0, %1, %2" : "=v"(nn) : "v"(m), "v"(limc));
+                    // one compare per step: nn == limc, written on the minimum's operands so that it does not wait for it, holds exactly
+                    // on the lanes that go on (limc == 32) or have nothing left of the query or of the target on their diagonal
+                    // (limc < 32); which of the two is looked at only when an active lane has it
                     x += nn; y += nn;
-                    more = snake_step_end(BALLOT(nn == limc), amask, nn, ended, rows_more);
+                    more = snake_step_end(BALLOT(limc <= m), amask, nn, ended, rows_more);
                 } while (more);
                 // one select per pass: the ring takes the low 16 bits of v, and an idle lane's m0 = sepv + y is about -2^29 (sep_word; its
                 // y is within +-2^17: x from 16 bits of the ring plus its snake, k2 a diagonal of the block)

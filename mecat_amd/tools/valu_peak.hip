@@ -127,6 +127,8 @@
 #define I_MINI(d, n) "v_min_i32 " d ", " d ", %12\n"
 #define I_MAX_I16(d, n) "v_max_i16 " d ", " d ", %12\n"
 #define I_ADD_U16(d, n) "v_add_u16 " d ", " d ", %12\n"
+#define I_MIN_U16(d, n) "v_min_u16 " d ", " d ", %12\n"
+#define I_ADD_LIT32(d, n) "v_add_u32 " d ", 0xffffff80, " d "\n"
 #define I_XNOR(d, n) "v_xnor_b32 " d ", " d ", %12\n"
 #define I_BCNT(d, n) "v_bcnt_u32_b32 " d ", " d ", %12\n"
 #define I_FFBL(d, n) "v_ffbl_b32 " d ", " n "\n"
@@ -194,7 +196,7 @@
     X(seq_v_cmp_sgpr_3cndmask, S8(I_CMP_3CNDMASK_SGPR), 32) X(seq_s_mov_vcc_cndmask, S8(I_SMOV_VCC_CNDMASK), 16)                 \
     X(mix_max_i16_add_u16, S8(I_MAX_I16_PAIR), 16) X(mix_3vadd_1vmax, S8(I_MIX_ADD_MAXI32), 32)                                   \
     X(v_lshrrev_b64, S8(I_LSHR_B64), 8) X(v_lshrrev_b64_sgpr, S8(I_LSHR_B64_S), 8) X(ds_write_b64, S8(I_DS_WRITE_B64) WAIT, 8)          \
-    X(s_bfm_b64, SS8(I_BFM), 8)                                                                                                   \
+    X(s_bfm_b64, SS8(I_BFM), 8) X(v_min_u16, S8(I_MIN_U16), 8) X(v_add_u32_lit32, S8(I_ADD_LIT32), 8)                              \
     X(mix_dw_rowbody, S8(I_MIX_DW) WAIT, 128)
 
 #define X_DEF(NAME, BODY, N) DEF_KERNEL(NAME, BODY)
