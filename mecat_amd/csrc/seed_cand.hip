@@ -2,6 +2,8 @@
 #include "seed_defs.h"
 #include "seed_replay.h"
 
+#define SWEEP_G 8       // neighbour segments of a sweep whose lists are in flight together
+
 struct CandLds {
     int t_loc[2 * SM + 10];
     int t_seed[2 * SM + 10];
@@ -45,7 +47,8 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(7, 7))) vo
                                                   int32_t* __restrict__ out_counts, unsigned long long* __restrict__ counters) {
     extern __shared__ __attribute__((aligned(16))) int smem[];
     const int lane = lane_id();
-    const int r = blockIdx.x;
+    // the batch's reads last-first: a read's subjects are the reads with lower ids, so the longest waves start first
+    const int r = (int)gridDim.x - 1 - (int)blockIdx.x;
     // the list: [maxc][12] in LDS; a list too long for that (-n above 1024: the reference takes any positive -n, pw_options.cpp:9) is
     // built in place in the read's slice of the output table — the same code on global memory, read past the L1 (the wave reads its
     // own earlier stores)
@@ -77,37 +80,53 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(7, 7))) vo
 #define SEG_LIST(g) (((seg_score[g] & OVF_FLAG) ? fin : ent) + seg_start[g])
 #define SEG_SCORE(g) (seg_score[g] & ~OVF_FLAG)
 #define SET_SCORE(g, v) seg_score[g] = (seg_score[g] & OVF_FLAG) | (v)
+#define HAS_LEFT 0x40000000           // (a segment id has 21 bits)
 
-        // The immutable part of the next gated segment's record (its index, segment ids, list starts) is fetched one iteration
-        // ahead: the walk is a chain of dependent loads (gated -> ids/starts -> scores -> lists), and the scores alone have to
-        // be read fresh (earlier iterations zero them).
-        int g_n = 0, seg_n = 0, segm1_n = -1;
-        uint32_t st_n = 0, stm1_n = 0;
-        auto prefetch = [&](int gi) {
-            g_n = (int)gated[gi];
-            seg_n = (int)seg_id[g_n];
-            st_n = seg_start[g_n];
-            segm1_n = g_n > 0 ? (int)seg_id[g_n - 1] : -1;
-            stm1_n = g_n > 0 ? seg_start[g_n - 1] : 0u;
-        };
-        if (ng > 0) prefetch(0);
+        // The walk is a chain of dependent loads from HBM (gated -> ids / starts -> scores -> lists), and its time is the number of
+        // round trips.  The gated list is taken in chunks of 64: lane j holds entry gi - gi % 64 + j — the immutable part of its
+        // record (table index, segment id with "the table's entry before it is the segment before it" in bit 30, the two list
+        // starts) and a copy of the two scores an iteration starts from.  The scores are the only part an earlier iteration changes
+        // (the sweeps and the self-hit scrub zero or lower them): the copy is loaded anew, one load per lane, behind every iteration
+        // that wrote one, so an entry that was zeroed costs its iteration no load at all, and a live one starts with its lists.
+        int gv = 0, segv = 0, scv = 0, scm1v = 0;
+        uint32_t stv = 0, stm1v = 0;
+        bool stale = true;
         for (int gi = 0; gi < ng; ++gi) {
-            const int g = g_n, seg = seg_n, segm1 = segm1_n;
-            const uint32_t st_g = st_n, st_gm1 = stm1_n;
-            if (gi + 1 < ng) prefetch(gi + 1);
+            const int gj = gi & 63;
+            if (gj == 0) {
+                gv = segv = 0;
+                stv = stm1v = 0;
+                if (gi + lane < ng) {
+                    gv = (int)gated[gi + lane];
+                    segv = (int)seg_id[gv];
+                    stv = seg_start[gv];
+                    const int segm1 = gv > 0 ? (int)seg_id[gv - 1] : -1;
+                    if (segv > 0 && gv > 0 && segm1 == segv - 1) { segv |= HAS_LEFT; stm1v = seg_start[gv - 1]; }
+                }
+                stale = true;
+            }
+            if (stale) {
+                scv = scm1v = 0;
+                if (gi - gj + lane < ng) {
+                    scv = seg_score[gv];
+                    if (segv & HAS_LEFT) scm1v = seg_score[gv - 1];
+                }
+                stale = false;
+            }
 #ifdef CAND_STATS
             if (lane == 0) atomicAdd(&counters[9], 1ull);
 #endif
-            const int raw_g = seg_score[g];
+            const int raw_g = __builtin_amdgcn_readlane(scv, gj);
             int s_k = raw_g & ~OVF_FLAG;
             if (s_k == 0) continue;
 #ifdef CAND_STATS
             if (lane == 0) atomicAdd(&counters[10], 1ull);
 #endif
+            const int g = __builtin_amdgcn_readlane(gv, gj), seg = __builtin_amdgcn_readlane(segv, gj) & ~HAS_LEFT;
+            const uint32_t st_g = (uint32_t)__builtin_amdgcn_readlane((int)stv, gj), st_gm1 = (uint32_t)__builtin_amdgcn_readlane((int)stm1v, gj);
+            const int raw_gm1 = __builtin_amdgcn_readlane(scm1v, gj);        // 0 without a left neighbour
+            const int loc = raw_gm1 & ~OVF_FLAG;
             int start_loc = seg * ZV;
-            int loc = 0, raw_gm1 = 0;
-            const bool has_left = seg > 0 && g > 0 && segm1 == seg - 1;
-            if (has_left) { raw_gm1 = seg_score[g - 1]; loc = raw_gm1 & ~OVF_FLAG; }
             if (loc > 0) start_loc = (seg - 1) * ZV;
             const int n1 = loc > 0 ? min(loc, SM) : 0, n2 = min(s_k, SM);
             const int k = n1 + n2;
@@ -193,10 +212,13 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(7, 7))) vo
                 else rep_loc = 63 - __clzll((unsigned long long)s0m);
             }
             const int vote = rep_loc < 64 ? __shfl(sc0, rep_loc) : __shfl(sc1, rep_loc - 64);
+            // (one LDS word each, the same in every lane: kept in scalar registers, and the geometry below with them)
+            const int loc_seed = __builtin_amdgcn_readfirstlane(T->t_seed[rep_loc]);
+            const int loc_list = start_loc + __builtin_amdgcn_readfirstlane(T->t_loc[rep_loc]);
+            // the subject lookup's first load, requested ahead of the threshold test (a location is a hit's: inside the volume)
+            const int blk_r = loc_list >= 0 ? (int)ref_blk[loc_list >> 10] : 0;
             if (vote < 2 * P.min_kmer_match + 2) continue;
-            const int loc_seed = T->t_seed[rep_loc];
-            const int loc_list = start_loc + T->t_loc[rep_loc];
-            int sid = read_id_lookup(ref_offs, ref_nreads, ref_blk, loc_list);
+            int sid = read_id_lookup_from(ref_offs, ref_nreads, blk_r, loc_list);
             const int sstart = ref_offs[sid].offset, ssize = ref_offs[sid].size;
             const int send = sstart + ssize + 1;
             sid += ref_start_id;
@@ -241,6 +263,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(7, 7))) vo
                     if (lane == 0) SET_SCORE(gg, __popcll(km));
                 }
                 __syncthreads();
+                stale = true;
                 continue;
             }
             // ---- geometry (pw_impl.cpp:386-403)
@@ -251,39 +274,65 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(7, 7))) vo
             if (num1 + num2 < P.min_kmer_dist) continue;
             // ---- neighbour sweeps (pw_impl.cpp:405-438), f64
             int seedcount = 0;
+            // A neighbour's test reads its own segment and writes its own score, so the order inside a sweep is free, and the two sweeps
+            // go together (seedcount is a sum).  Round c takes 32 neighbours of either side: lane j < 32 owns the left neighbour
+            // x = g - 1 - 32 c - j, lane 32 + j the right one x = g + 1 + 32 c + j, and loads its table entry: one round trip for both
+            // sides.  The lists of the live ones are then requested SWEEP_G segments at a time, left side first, before the first of
+            // them is tested: one more.  A segment's agreeing entries are counted into its owner's lane, and the owners zero the
+            // scores at the round's end.
             {
-                int nlb = (num1 + ZV - 1) / ZV;
+                const int nlb = (num1 + ZV - 1) / ZV, nrb = (num2 + ZV - 1) / ZV;
                 const int lowest = max(0, seg - nlb);          // segments seg-1 .. lowest
-                for (int x = g - 1; x >= 0 && (int)seg_id[x] >= lowest; --x) {
-                    const int sc = SEG_SCORE(x);
-                    if (sc <= 0) continue;
-                    const int sl = (int)seg_id[x] * ZV, scnt = min(sc, SM);
-                    bool ok = false;
-                    if (lane < scnt) {
-                        uint32_t e = SEG_LIST(x)[lane];
-                        ok = fabs((double)(loc_list - sl - ent_loc(e)) / ((double)((loc_seed - ent_seed(e)) * BC) * 1.0) - 1.0) < cutoff;
-                    }
-                    const int agree = __popcll(__ballot(ok));
-                    seedcount += agree;
-                    if (agree * 1.0 / scnt > 0.4) { if (lane == 0) SET_SCORE(x, 0); }
-                    __syncthreads();
-                }
-                int nrb = (num2 + ZV - 1) / ZV;
                 const int highest = seg + nrb;                  // segments seg+1 .. highest
-                for (int x = g + 1; x < nseg && (int)seg_id[x] <= highest; ++x) {
-                    const int sc = SEG_SCORE(x);
-                    if (sc <= 0) continue;
-                    const int sl = (int)seg_id[x] * ZV, scnt = min(sc, SM);
-                    bool ok = false;
-                    if (lane < scnt) {
-                        uint32_t e = SEG_LIST(x)[lane];
-                        ok = fabs((double)(sl + ent_loc(e) - loc_list) / ((double)((ent_seed(e) - loc_seed) * BC) * 1.0) - 1.0) < cutoff;
+                const bool lside = lane < 32;
+                uint64_t more = ~0ull;                          // the lanes of a side that may have neighbours left
+                for (int c = 0; more; ++c) {
+                    const int x = lside ? g - 1 - 32 * c - lane : g + 1 + 32 * c + (lane - 32);
+                    int id = -1, raw = 0;
+                    uint32_t st = 0;
+                    if (((more >> lane) & 1) && x >= 0 && x < nseg) { id = (int)seg_id[x]; raw = seg_score[x]; st = seg_start[x]; }
+                    // the table ascends: the neighbours inside a sweep's reach are the first lanes of its side
+                    const bool in = id >= 0 && (lside ? id >= lowest : id <= highest);
+                    const uint64_t inm = __builtin_amdgcn_ballot_w64(in);
+                    more = ((uint32_t)inm == 0xFFFFFFFFu ? 0xFFFFFFFFull : 0ull) | ((uint32_t)(inm >> 32) == 0xFFFFFFFFu ? 0xFFFFFFFF00000000ull : 0ull);
+                    const int scnt = min(raw & ~OVF_FLAG, SM);
+                    const uint64_t live = __builtin_amdgcn_ballot_w64(in && (raw & ~OVF_FLAG) > 0);
+                    int agv = 0;
+                    uint64_t m = live;
+                    while (m) {
+                        uint32_t e[SWEEP_G];
+                        uint64_t p = m;
+#pragma unroll
+                        for (int q = 0; q < SWEEP_G; ++q) {      // (no branch on a slot without a segment: no lane loads)
+                            const bool has = p != 0;
+                            const int j = has ? __builtin_ctzll(p) : 0;
+                            p &= p - 1;
+                            const int rj = __builtin_amdgcn_readlane(raw, j);
+                            const uint32_t* L = ((rj & OVF_FLAG) ? fin : ent) + (uint32_t)__builtin_amdgcn_readlane((int)st, j);
+                            e[q] = 0;
+                            if (has && lane < min(rj & ~OVF_FLAG, SM)) e[q] = L[lane];
+                        }
+#pragma unroll
+                        for (int q = 0; q < SWEEP_G; ++q) {
+                            if (m) {
+                                const int j = __builtin_ctzll(m);
+                                m &= m - 1;
+                                const int sl = __builtin_amdgcn_readlane(id, j) * ZV, sc = __builtin_amdgcn_readlane(scnt, j);
+                                const int l = ent_loc(e[q]), sd = ent_seed(e[q]);
+                                const int dl = j < 32 ? loc_list - sl - l : sl + l - loc_list;
+                                const int ds = j < 32 ? loc_seed - sd : sd - loc_seed;
+                                const bool ok = lane < sc && fabs((double)dl / ((double)(ds * BC) * 1.0) - 1.0) < cutoff;
+                                const int agree = __popcll(__builtin_amdgcn_ballot_w64(ok));
+                                seedcount += agree;
+                                agv = write_lane(agree, j, agv);
+                            }
+                        }
                     }
-                    const int agree = __popcll(__ballot(ok));
-                    seedcount += agree;
-                    if (agree * 1.0 / scnt > 0.4) { if (lane == 0) SET_SCORE(x, 0); }
-                    __syncthreads();
+                    const bool zero = ((live >> lane) & 1) && agv * 1.0 / scnt > 0.4;
+                    if (zero) seg_score[x] = raw & OVF_FLAG;
+                    stale |= __builtin_amdgcn_ballot_w64(zero) != 0;
                 }
+                if (stale) __syncthreads();
             }
             const int cscore = vote + seedcount;
             // ---- stable insertion into the descending top-MAXC list (pw_impl.cpp:442-455)
@@ -318,6 +367,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(7, 7))) vo
 #undef SEG_LIST
 #undef SEG_SCORE
 #undef SET_SCORE
+#undef HAS_LEFT
     }
     __syncthreads();
     int* o = (int*)(out + (size_t)r * MAXC);

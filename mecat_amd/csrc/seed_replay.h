@@ -1,7 +1,8 @@
 // seed_replay.h — device helpers of the seeding stage that more than one kernel family calls (seed_defs.h lists the families):
 //   sweep_reach                    seed_filter, seed_filter_wide, seed_strand
 //   ddf_insert, replay_overflow    seed_build, seed_strand
-//   read_id_lookup                 seed_cand, and through subjects_all_higher seed_build and seed_strand
+//   read_id_lookup                 through subjects_all_higher seed_build and seed_strand
+//   read_id_lookup_from            seed_cand
 #pragma once
 
 #include "seed_defs.h"
@@ -115,6 +116,16 @@ __device__ __forceinline__ int read_id_from_offset(const mhip_offset_t* __restri
 __device__ __forceinline__ int read_id_lookup(const mhip_offset_t* __restrict__ a, int n, const uint32_t* __restrict__ blk, int offset) {
     if (offset >= 0) {
         int r = (int)blk[offset >> 10];
+        while (r + 1 < n && a[r].offset + a[r].size <= offset) ++r;
+        const int o = a[r].offset, z = a[r].size;
+        if (o <= offset && o + z > offset) return r;
+    }
+    return read_id_from_offset(a, n, offset);
+}
+
+// read_id_lookup with its first load made by the caller: r = blk[offset >> 10] (any value where offset < 0)
+__device__ __forceinline__ int read_id_lookup_from(const mhip_offset_t* __restrict__ a, int n, int r, int offset) {
+    if (offset >= 0) {
         while (r + 1 < n && a[r].offset + a[r].size <= offset) ++r;
         const int o = a[r].offset, z = a[r].size;
         if (o <= offset && o + z > offset) return r;
