@@ -349,6 +349,52 @@ int  mhip_ref_extend_fetch(mhip_ctx* ctx, mhip_ref_result* res /*[n][maxc]*/, ui
 /* measurement hook: of the last mhip_ref_extend_run* call — [0] slots, [1] slices, [2] bytes of row scratch, [3] words of the column store */
 void mhip_ref_extend_stats(int64_t out[4]);
 
+/* ---- mecat2ref, stage 3: the clipped-alignment rescue and the result order (PacBio mode) ----
+ * Replaces everything of reference_mapping between its extension loop and the per-thread result file (mecat2ref_impl_large.cpp:584-603
+ * for round 1, :847-866 for round 2): rescue_clipped_align (mecat2ref/mecat2ref_aux.cpp:308-452) with find_left_clipped_candidate /
+ * find_right_clipped_candidate / fill_clipped_candidate (:185-274), is_left_clipped_align / is_right_clipped_align (:276-306),
+ * is_full_align and AlignInfoContained (mecat2ref_aux.h:22-42), and output_results (:454-473).  Input: the results of the read's first
+ * list (mhip_ref_extend_run's, maxc <= 10).  The searches need the per-segment seed records (Back_List) of the strands that own one of a
+ * read's first three entries; stage 1 does not keep them, so its seeding loop (mecat2ref_impl_large.cpp:417-453) runs again for the reads
+ * the tool does not return early on.  The rescue candidates (at most 6 per read, in the tool's call order) go through the same
+ * extension as the lists, into a second set of buffers: mhip_ref_extend_fetch still returns the first extension afterwards.
+ * A record is named by its slot: [0, maxc) is a slot of the read's first list (mhip_ref_extend_fetch's res[n][maxc]), maxc + j is rescue
+ * slot j of the read.  out_slots[n][3 * num_output] holds, per read, the slots in the order output_results prints their records
+ * (out_counts[n] of them, the rest -1): mecat_amd/host/ref_results.h writes the records.
+ * mhip_ref_rescue_state, what :328-341 leave: naln surviving entries in the sorted order, entry k = list slot slot[k] with the tool's id
+ * id[k] (its index among the read's ok results); nres = ok results of the first list (the id the first ok rescue result takes); qs = the
+ * read's length; go_on = 0 when the tool returns at :341 (the longest entry covers 0.9 of the read) or there is no entry.
+ * Refused with a message and -1, the context stays usable: tech != 0, maxc outside 1..10 (std::sort's order of equal lengths is
+ * reproduced for at most 16 entries), num_output < 1, round outside 0..1, a read of 100 000 letters or more, an index that was not
+ * built from this reference. */
+typedef struct { int32_t maxc, round, num_output, tech; double ddfs_cutoff; } mhip_ref_rescue_params;
+typedef struct { int32_t naln, go_on, nres, qs; int8_t slot[16], id[16]; } mhip_ref_rescue_state;
+/* maxc 10 (kDefaultNumCandidates, mecat2ref.cpp:18), round 0, num_output 10 (kDefaultNumOutput, :19), tech, ddfs_cutoff 0.25 */
+void mhip_ref_rescue_params_default(mhip_ref_rescue_params* p, int tech);
+/* res: HOST results [n][maxc] of reads [rid_begin, rid_end) (mhip_ref_extend_fetch's layout); total_words = the words the ok rescue results take */
+int  mhip_ref_rescue_run(mhip_ctx* ctx, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end,
+                         const mhip_ref_rescue_params* params, const mhip_ref_result* res /*[n][maxc]*/, int64_t* total_words);
+/* the same on DEVICE results; d_res = NULL: the results of the last mhip_ref_extend_run* on this context (refused if that run's slots
+ * are not n * maxc) */
+int  mhip_ref_rescue_run_dev(mhip_ctx* ctx, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end,
+                             const mhip_ref_rescue_params* params, const mhip_ref_result* d_res, int64_t* total_words);
+/* same context, before the next mhip_ref_rescue_run*: rescue_cands / rescue_res [n][6] (entries behind rescue_counts[i] are undefined),
+ * word_offs[6 n + 1] and ops_dense[total_words] as mhip_ref_extend_fetch gives them for the rescue results */
+int  mhip_ref_rescue_fetch(mhip_ctx* ctx, int32_t* out_slots /*[n][3 * num_output]*/, int32_t* out_counts, mhip_ref_candidate* rescue_cands,
+                           int32_t* rescue_counts, mhip_ref_result* rescue_res, uint64_t* word_offs, uint32_t* ops_dense);
+/* measurement hook: of the last mhip_ref_rescue_run* call — [0] reads, [1] reads that went on past :341, [2] rescue candidates,
+ * [3] reads redone with full record pools */
+void mhip_ref_rescue_stats(int64_t out[4]);
+/* test hook: ref_rescue_prep (:328-341) on host results res[n][maxc] -> states[n] */
+int  mhip_debug_ref_rescue_prep(mhip_ctx* ctx, const mhip_ref_rescue_params* params, int n, const mhip_ref_result* res /*[n][maxc]*/,
+                                mhip_ref_rescue_state* states /*[n]*/);
+/* test hook: ref_rescue_finish — the attach tests of :380-399 / :416-435 on the rescue results in call order, :438-451 and
+ * output_results — on hand-made states and rescue results.  rescue_meta[n][6]: owner entry (place in the state's order, 0..2) |
+ * side << 8 (0 left, 1 right); rescue_res[n][6]; out_slots[n][3 * num_output] (unused places -1), out_counts[n] = records printed. */
+int  mhip_debug_ref_rescue_finish(mhip_ctx* ctx, const mhip_ref_rescue_params* params, int n, const mhip_ref_result* res /*[n][maxc]*/,
+                                  const mhip_ref_rescue_state* states, const int32_t* rescue_counts, const int32_t* rescue_meta,
+                                  const mhip_ref_result* rescue_res, int32_t* out_slots, int32_t* out_counts);
+
 /* mhip_index_build by all ranks of the communicator together (replaces create_ref_index, common/lookup_table.cpp:63-160, in a
  * multi-GPU cell): the 4^13 key space is cut into P contiguous ranges of equal occupancy, each rank builds the buckets of its range,
  * positions and table slices are all-gathered (counts first, then payload), and every rank returns the complete table — equal, array

@@ -6,9 +6,10 @@ the multi-GPU launcher; it contains no compute and has NO CPU fallback: importin
 shared library is missing, and every call raises MhipError if no gfx950 device is usable.
 """
 from .hip import (  # noqa: F401
-    Candidate, AlnJob, AlnResult, Context, Index, MhipError, Params, RefCandidate, RefSeedParams, Volume, lib, lib_path, ref_seed_params,
-    ref_extend, ref_seed_reads,
+    Candidate, AlnJob, AlnResult, Context, Index, MhipError, Params, RefCandidate, RefRescueParams, RefSeedParams, Volume, lib, lib_path,
+    ref_rescue_fetch, ref_rescue_params, ref_rescue_run, ref_rescue_run_dev, ref_seed_params, ref_extend, ref_seed_reads,
 )
 
-__all__ = ["Candidate", "AlnJob", "AlnResult", "Context", "Index", "MhipError", "Params", "RefCandidate", "RefSeedParams", "Volume", "lib",
-           "lib_path", "ref_extend", "ref_seed_params", "ref_seed_reads"]
+__all__ = ["Candidate", "AlnJob", "AlnResult", "Context", "Index", "MhipError", "Params", "RefCandidate", "RefRescueParams", "RefSeedParams", "Volume",
+           "lib", "lib_path", "ref_extend", "ref_rescue_fetch", "ref_rescue_params", "ref_rescue_run", "ref_rescue_run_dev",
+           "ref_seed_params", "ref_seed_reads"]

@@ -67,10 +67,13 @@ struct mhip_ctx {
     size_t as_clean_nrec = 0;
     int ae_n = 0;                         // jobs and dense words of the last mhip_asm_extend_run (what mhip_asm_extend_fetch copies)
     int64_t ae_total = 0;
-    int rx_slots = 0;                     // slots and dense words of the last mhip_ref_extend_run (what mhip_ref_extend_fetch copies)
-    int64_t rx_total = 0;
-    bool rx_on_host = false;              // a run of several slices: the dense words are in rx_words already
-    std::vector<uint32_t> rx_words;
+    // slots and dense words of the last extension of mecat2ref's candidates, per buffer set: [0] mhip_ref_extend_run (what
+    // mhip_ref_extend_fetch copies), [1] the rescue candidates' extension inside mhip_ref_rescue_run (mhip_ref_rescue_fetch)
+    int rx_slots[2] = {0, 0};
+    int64_t rx_total[2] = {0, 0};
+    bool rx_on_host[2] = {false, false};  // a run of several slices: the dense words are in rx_words already
+    std::vector<uint32_t> rx_words[2];
+    int rr_n = 0, rr_num_output = 0;      // reads and num_output of the last mhip_ref_rescue_run (what mhip_ref_rescue_fetch copies)
     int ix_s1_ranges = -1;               // index build, ix_scatter1's tile order: -1 not measured yet, 0 tile = block, 1 a contiguous eighth of the tiles per XCD
 
     // returns a device buffer of at least `bytes` (contents undefined)

@@ -38,6 +38,7 @@
 #include <algorithm>
 
 #include "dw_helpers.h"
+#include "ref_extend.h"
 #include "scan.h"
 
 #define RX_BLOCK 256
@@ -420,11 +421,15 @@ __global__ __launch_bounds__(256) void ref_join(const mhip_ref_result* __restric
     }
 }
 
-int64_t g_last_stats[4] = {0, 0, 0, 0};      // of the last run: jobs, slices, bytes of row scratch, words of the column store
+int64_t g_last_stats[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};      // of the last run into each buffer set: jobs, slices, bytes of row scratch, words of the column store
 
+}  // namespace
+
+// Results, word offsets and dense words go to buffer set `set` (ref_extend.h) and stay there until the next run into the same set;
+// everything else is working memory shared by the sets.
 int ref_extend_run(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, int maxc, int tech,
-                   const mhip_ref_candidate* d_cands, const int32_t* d_counts, int64_t* total_words) {
-    c->rx_slots = 0; c->rx_total = 0; c->rx_on_host = false;
+                   const mhip_ref_candidate* d_cands, const int32_t* d_counts, int64_t* total_words, int set) {
+    c->rx_slots[set] = 0; c->rx_total[set] = 0; c->rx_on_host[set] = false;
     if (total_words) *total_words = 0;
     if (tech != 0) {
         mhip_set_error("mhip_ref_extend_run: tech = %d: only PacBio mode (tech 0, DiffAligner) is built; nanopore mode needs the X-drop aligner's aligned strings", tech);
@@ -438,7 +443,7 @@ int ref_extend_run(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads
             return -1;
         }
     const int n = rid_end - rid_begin;
-    g_last_stats[0] = g_last_stats[1] = g_last_stats[2] = g_last_stats[3] = 0;
+    for (int i = 0; i < 4; ++i) g_last_stats[set][i] = 0;
     if (n == 0) return 0;
     const int slots = n * maxc;
     const long long units = 2ll * slots;
@@ -452,10 +457,10 @@ int ref_extend_run(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads
     if (c->scratch("rx_words", sizeof(uint32_t) * (size_t)units, (void**)&d_words)) return -1;
     if (c->scratch("rx_rwords", sizeof(uint32_t) * (size_t)slots, (void**)&d_rwords)) return -1;
     if (c->scratch("rx_dbase", sizeof(unsigned long long) * (size_t)(units + 1), (void**)&d_dbase)) return -1;
-    if (c->scratch("rx_woffs", sizeof(unsigned long long) * (size_t)(slots + 1), (void**)&d_woffs)) return -1;
+    if (scratch_set(c, "rx_woffs", set, sizeof(unsigned long long) * (size_t)(slots + 1), (void**)&d_woffs)) return -1;
     if (c->scratch("rx_swoffs", sizeof(unsigned long long) * (size_t)(slots + 1), (void**)&d_swoffs)) return -1;
     if (c->scratch("rx_dres", sizeof(RxDir) * (size_t)units, (void**)&d_dres)) return -1;
-    if (c->scratch("rx_res", sizeof(mhip_ref_result) * (size_t)slots, (void**)&d_res)) return -1;
+    if (scratch_set(c, "rx_res", set, sizeof(mhip_ref_result) * (size_t)slots, (void**)&d_res)) return -1;
     if (c->scratch("rx_cursor", 64, (void**)&d_cur)) return -1;
     HIPCHK(hipMemsetAsync(d_cur, 0, 64, c->stream));
     LAUNCH(c, "ref_jobs", ref_jobs, (slots + 255) / 256, 256, 0, d_cands, d_counts, n, maxc, rid_begin, (const mhip_offset_t*)reads->d_offs,
@@ -497,13 +502,13 @@ int ref_extend_run(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads
     uint32_t *d_store, *d_dense;
     if (c->scratch("rx_store", sizeof(uint32_t) * (size_t)(store_words + 1), (void**)&d_store)) return -1;
     // an ok result's words are no more than its two directions' bounds: the dense output of a slice fits what its store takes
-    if (c->scratch("rx_dense", sizeof(uint32_t) * (size_t)(store_words + 1), (void**)&d_dense)) return -1;
+    if (scratch_set(c, "rx_dense", set, sizeof(uint32_t) * (size_t)(store_words + 1), (void**)&d_dense)) return -1;
     const int max_waves = c->num_cus * 16;               // 4 waves per SIMD, as dw_extend; LDS 5.6 KB per wave
     uint16_t* d_g;
     if (c->scratch("rx_rows", sizeof(uint16_t) * RX_GROW * (size_t)max_waves, (void**)&d_g)) return -1;
-    g_last_stats[0] = slots; g_last_stats[1] = nslices; g_last_stats[2] = (int64_t)(sizeof(uint16_t) * RX_GROW * (size_t)max_waves);
-    g_last_stats[3] = (int64_t)store_words;
-    if (nslices > 1) c->rx_words.clear();
+    g_last_stats[set][0] = slots; g_last_stats[set][1] = nslices; g_last_stats[set][2] = (int64_t)(sizeof(uint16_t) * RX_GROW * (size_t)max_waves);
+    g_last_stats[set][3] = (int64_t)store_words;
+    if (nslices > 1) c->rx_words[set].clear();
     unsigned long long wbase = 0;
     for (int i = 0; i < nslices; ++i) {
         const int s0 = cuts[(size_t)i], s1 = cuts[(size_t)i + 1];
@@ -526,24 +531,39 @@ int ref_extend_run(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads
         HIPCHK(hipMemcpyAsync(&wend, d_swoffs + (s1 - s0), sizeof(wend), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         if (nslices > 1) {                               // the dense buffer is the next slice's: its words leave the device now
-            c->rx_words.resize((size_t)wend);
-            if (wend > wbase) HIPCHK(hipMemcpy(c->rx_words.data() + wbase, d_dense, sizeof(uint32_t) * (size_t)(wend - wbase), hipMemcpyDeviceToHost));
+            c->rx_words[set].resize((size_t)wend);
+            if (wend > wbase) HIPCHK(hipMemcpy(c->rx_words[set].data() + wbase, d_dense, sizeof(uint32_t) * (size_t)(wend - wbase), hipMemcpyDeviceToHost));
         }
         wbase = wend;
     }
-    c->rx_slots = slots; c->rx_total = (int64_t)wbase; c->rx_on_host = nslices > 1;
+    c->rx_slots[set] = slots; c->rx_total[set] = (int64_t)wbase; c->rx_on_host[set] = nslices > 1;
     if (total_words) *total_words = (int64_t)wbase;
     return 0;
 }
 
-}  // namespace
+int ref_extend_fetch(mhip_ctx* c, int set, mhip_ref_result* res, uint64_t* word_offs, uint32_t* ops_dense) {
+    const int slots = c->rx_slots[set];
+    if (slots == 0) { if (word_offs) word_offs[0] = 0; return 0; }
+    mhip_ref_result* d_res;
+    unsigned long long* d_woffs;
+    uint32_t* d_dense;
+    if (scratch_set(c, "rx_res", set, 0, (void**)&d_res) || scratch_set(c, "rx_woffs", set, 0, (void**)&d_woffs) || scratch_set(c, "rx_dense", set, 0, (void**)&d_dense)) return -1;
+    HIPCHK(hipMemcpyAsync(res, d_res, sizeof(mhip_ref_result) * (size_t)slots, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(word_offs, d_woffs, sizeof(uint64_t) * (size_t)(slots + 1), hipMemcpyDeviceToHost, c->stream));
+    if (c->rx_total[set] > 0) {
+        if (c->rx_on_host[set]) memcpy(ops_dense, c->rx_words[set].data(), sizeof(uint32_t) * (size_t)c->rx_total[set]);
+        else HIPCHK(hipMemcpyAsync(ops_dense, d_dense, sizeof(uint32_t) * (size_t)c->rx_total[set], hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
 
 extern "C" {
 
 int mhip_ref_extend_run_dev(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, int maxc, int tech,
                             const mhip_ref_candidate* d_cands, const int32_t* d_counts, int64_t* total_words) {
     HIPCHK(hipSetDevice(c->device));
-    return ref_extend_run(c, ref, reads, rid_begin, rid_end, maxc, tech, d_cands, d_counts, total_words);
+    return ref_extend_run(c, ref, reads, rid_begin, rid_end, maxc, tech, d_cands, d_counts, total_words, 0);
 }
 
 int mhip_ref_extend_run(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, int maxc, int tech,
@@ -559,29 +579,16 @@ int mhip_ref_extend_run(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* 
         HIPCHK(hipMemcpyAsync(d_n, counts, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));       // (the caller's arrays are read until here)
     }
-    return ref_extend_run(c, ref, reads, rid_begin, rid_end, maxc, tech, d_c, d_n, total_words);
+    return ref_extend_run(c, ref, reads, rid_begin, rid_end, maxc, tech, d_c, d_n, total_words, 0);
 }
 
 int mhip_ref_extend_fetch(mhip_ctx* c, mhip_ref_result* res, uint64_t* word_offs, uint32_t* ops_dense) {
     HIPCHK(hipSetDevice(c->device));
-    const int slots = c->rx_slots;
-    if (slots == 0) { if (word_offs) word_offs[0] = 0; return 0; }
-    mhip_ref_result* d_res;
-    unsigned long long* d_woffs;
-    uint32_t* d_dense;
-    if (c->scratch("rx_res", 0, (void**)&d_res) || c->scratch("rx_woffs", 0, (void**)&d_woffs) || c->scratch("rx_dense", 0, (void**)&d_dense)) return -1;
-    HIPCHK(hipMemcpyAsync(res, d_res, sizeof(mhip_ref_result) * (size_t)slots, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(word_offs, d_woffs, sizeof(uint64_t) * (size_t)(slots + 1), hipMemcpyDeviceToHost, c->stream));
-    if (c->rx_total > 0) {
-        if (c->rx_on_host) memcpy(ops_dense, c->rx_words.data(), sizeof(uint32_t) * (size_t)c->rx_total);
-        else HIPCHK(hipMemcpyAsync(ops_dense, d_dense, sizeof(uint32_t) * (size_t)c->rx_total, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    return ref_extend_fetch(c, 0, res, word_offs, ops_dense);
 }
 
 void mhip_ref_extend_stats(int64_t out[4]) {
-    for (int i = 0; i < 4; ++i) out[i] = g_last_stats[i];
+    for (int i = 0; i < 4; ++i) out[i] = g_last_stats[0][i];          // (set 0: the rescue's own extension does not show here)
 }
 
 }  // extern "C"

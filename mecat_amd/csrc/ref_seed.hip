@@ -27,6 +27,8 @@
 // Mapping: one wave per query read, persistent, reads from an atomic cursor; everything order dependent in the reference's order with
 // the wave's lanes inside each step (asm_seed.hip's scheme: a bucket 64 entries at a time, the first lane of a run of one segment is
 // the hit that can be a seed, first-touch order by ballot prefix).  insert_loc and find_location vote with one list entry per lane.
+// The segment array, the seeding loop, the vote and find_location's choice live in ref_seed_dev.h: ref_rescue.hip (stage 3) builds a
+// strand's records again with the same code for its searches.
 // Parity: tests/test_gpu_ref_seed.py against tests/golden/ref_cand.npz (recorded from the unmodified mecat2ref) and tests/ref_cand_ref.py.
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,66 +36,9 @@
 #include <algorithm>
 #include <vector>
 
-#include "common.h"
-
-#define RF_SM 20                     // seeds stored per segment (SM, mecat2ref_defs.h:22)
-#define RF_MAXC 100                  // longest list a call may ask for
-#define RF_RM 100000                 // the reference's read buffers (RM, mecat2ref_defs.h:16)
-#define RF_REC 44                    // shorts of one record: score, loczhi[20], seedno[20], seednum, index (two shorts)
-#define R_SCORE 0
-#define R_LOC 1
-#define R_SEED (1 + RF_SM)
-#define R_SEEDNUM (1 + 2 * RF_SM)
-#define R_INDEX (2 + 2 * RF_SM)      // int at short offset 42 (byte 84)
-#define RF_BLOCK 256
-#define RF_POOL 2048                 // records of a wave's pool (176 KB); a read that needs more is redone with a worst-case pool
-#define RF_WAVES (RF_BLOCK / WAVE)
+#include "ref_seed_dev.h"
 
 namespace {
-
-struct RefWaveLds {
-    int tl[64], ts[64], tsc[64];     // find_location's lists (at most 2 * 20 entries) / insert_loc's 21
-    mhip_ref_candidate cand[RF_MAXC];
-};
-
-typedef volatile short vshort;       // the segment records are re-read after other lanes wrote them: no L1 / register caching
-
-__device__ __forceinline__ int rf_index(vshort* r) { return (int)(uint16_t)r[R_INDEX] | ((int)r[R_INDEX + 1] << 16); }
-__device__ __forceinline__ void rf_set_index(vshort* r, int v) { r[R_INDEX] = (short)(v & 0xffff); r[R_INDEX + 1] = (short)(v >> 16); }
-
-__device__ __forceinline__ void rf_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// the DDF test of find_location (mecat2ref_aux.cpp:10: fabs(int / (int * float) - 1) < double, all f32 up to the comparison) and of
-// insert_loc (mecat2ref_impl_large.cpp:106: `- 1.0`, so the subtraction is f64)
-template <bool SUB_F64>
-__device__ __forceinline__ bool rf_ddf(int dloc, int dseed, float bc, double cutoff) {
-    const float q = (float)dloc / ((float)dseed * bc);
-    if (SUB_F64) return fabs((double)q - 1.0) < cutoff;
-    return (double)fabsf(q - 1.0f) < cutoff;
-}
-
-// the pairwise vote over S.tl / S.ts [0, n), n <= 64: entry i per lane, its j > i in order; votes into S.tsc (zeroed by the caller).
-// dist_cap: find_location's `t_loc[j] - t_loc[i] < read_len`; insert_loc has no such term.
-template <bool SUB_F64>
-__device__ __forceinline__ void rf_vote(RefWaveLds& S, int n, int lane, float bc, double cutoff, int dist_cap) {
-    if (lane < n - 1) {
-        const int li = S.tl[lane], si = S.ts[lane];
-        int mine = 0;
-        for (int j = lane + 1; j < n; ++j) {
-            const int dl = S.tl[j] - li, ds = S.ts[j] - si;
-            if (ds > 0 && dl > 0 && dl < dist_cap && rf_ddf<SUB_F64>(dl, ds, bc, cutoff)) {
-                ++mine;
-                atomicAdd(&S.tsc[j], 1);
-            }
-        }
-        if (mine) atomicAdd(&S.tsc[lane], mine);
-    }
-    __builtin_amdgcn_wave_barrier();
-}
 
 __global__ __launch_bounds__(RF_BLOCK) void ref_seed(const uint32_t* __restrict__ starts, const int32_t* __restrict__ offsets, const uint32_t* __restrict__ qpac,
                                                     const uint32_t* __restrict__ qnpac, const mhip_offset_t* __restrict__ qoffs, int rid_begin, int n,
@@ -105,25 +50,11 @@ __global__ __launch_bounds__(RF_BLOCK) void ref_seed(const uint32_t* __restrict_
     RefWaveLds& S = lds[threadIdx.x >> 6];
     const int lane = lane_id();
     const size_t gw = (size_t)blockIdx.x * RF_WAVES + (threadIdx.x >> 6);
-    vshort* pool = pool_all + gw * (size_t)pcap * RF_REC;                  // pcap records; record 0 = the untouched record
-    volatile uint32_t* dir = dir_all + gw * (size_t)(nseg + 8);
-    int* ilist = ilist_all + gw * (size_t)pcap;
-    volatile short* iscore = iscore_all + gw * (size_t)pcap;
-    volatile int* slotseg = slotseg_all + gw * (size_t)pcap;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    auto rec = [&](int seg) { return pool + (size_t)dir[seg] * RF_REC; };
-    // records [0, hw) of the pool have been initialised and are in the untouched state
-    int hw = hw_all[gw];
-    auto init_records = [&](int from, int to) {
-        for (int r = from; r < to; ++r) {
-            vshort* q = pool + (size_t)r * RF_REC;
-            if (lane < RF_REC - 2) q[lane] = 0;
-            if (lane == 0) rf_set_index(q, -1);
-        }
-    };
-    if (hw == 0) { init_records(0, 1); hw = 1; }
-    int nslots = 1;                                                      // records handed out to the strand in hand: [1, nslots)
-    rf_sync();
+    RfWave W;
+    W.bind(gw, pool_all, dir_all, hw_all, ilist_all, iscore_all, slotseg_all, nseg, pcap, lane);
+    auto rec = [&](int seg) { return W.rec(seg); };
+    int* const ilist = W.ilist;
+    volatile short* const iscore = W.iscore;
 
     while (true) {
         unsigned int u = 0;
@@ -142,112 +73,8 @@ __global__ __launch_bounds__(RF_BLOCK) void ref_seed(const uint32_t* __restrict_
         bool ovf = false;                    // the read needs more records than the pool has: given up here, redone by the launch with full pools
         for (int strand = 0; strand < 2 && !ovf; ++strand) {
             int touched = 0;
-            // ---- seeding (:417-453).  Bucket bounds two steps ahead and first positions one step ahead, as in asm_seed.hip.
-            auto bounds = [&](int k, uint32_t& s0, uint32_t& s1) {
-                s0 = s1 = 0;
-                if (k >= K) return;
-                const int64_t kpos = !strand ? qoff + (int64_t)k * bcq : qoff + L - MHIP_KMER_SIZE - (int64_t)k * bcq;
-                // a k-mer with a letter other than upper-case A, C, G, T is not looked up (atcttrans gives 4, :44-51, :79-83)
-                if (qnpac && pac_kmer(qnpac, kpos) != 0u) return;
-                const uint32_t id = !strand ? pac_kmer(qpac, kpos) : kmer_revcomp(pac_kmer(qpac, kpos));
-                s0 = starts[id];
-                s1 = starts[id + 1];
-            };
-            uint32_t s0, s1, n0, n1;
-            bounds(0, s0, s1);
-            bounds(1, n0, n1);
-            int pfirst = s0 + (uint32_t)lane < s1 ? offsets[s0 + (uint32_t)lane] : 0;
-            for (int k = 0; k < K; ++k) {
-                const int pnext = n0 + (uint32_t)lane < n1 ? offsets[n0 + (uint32_t)lane] : 0;
-                uint32_t m0, m1;
-                bounds(k + 2, m0, m1);
-                int carry_seg = -1;
-                for (uint32_t base = s0; base < s1; base += 64) {
-                    const uint32_t e = base + (uint32_t)lane;
-                    const bool valid = e < s1;
-                    const int p = valid ? (base == s0 ? pfirst : offsets[e]) + 1 : 0;          // 1-based k-mer start (i + 2 - seed_len, :265)
-                    const int seg = valid ? p / Z : -2, off = p % Z;
-                    int seg_prev = __shfl_up(seg, 1);
-                    if (lane == 0) seg_prev = carry_seg;
-                    carry_seg = __shfl(seg, 63);
-                    const bool head = valid && seg != seg_prev;        // the first hit of this k-mer in its segment
-                    bool ev = false;
-                    int newscore = 0;
-                    // a segment's first hit takes the next record of the pool
-                    const bool fresh_rec = head && dir[seg] == 0u;
-                    const unsigned long long fm = __ballot(fresh_rec);
-                    if (fm && nslots + (int)__popcll(fm) > pcap) { ovf = true; break; }
-                    if (fm) {
-                        const int nnew = (int)__popcll(fm);
-                        if (nslots + nnew > hw) {
-                            init_records(hw, nslots + nnew);
-                            hw = nslots + nnew;
-                            rf_sync();
-                        }
-                        if (fresh_rec) {
-                            const int sl = nslots + (int)__popcll(fm & below);
-                            dir[seg] = (uint32_t)sl;
-                            slotseg[sl] = seg;
-                        }
-                        nslots += nnew;
-                    }
-                    if (head) {
-                        vshort* r = rec(seg);
-                        const int sc = r[R_SCORE], sn = r[R_SEEDNUM];
-                        ev = sc == 0 || sn < k + 1;                    // :429
-                        if (ev) {
-                            newscore = sc + 1;
-                            r[R_SCORE] = (short)newscore;
-                            if (newscore <= RF_SM) { r[R_LOC + newscore - 1] = (short)off; r[R_SEED + newscore - 1] = (short)(k + 1); }
-                        }
-                        r[R_SEEDNUM] = (short)(k + 1);
-                    }
-                    // insert_loc (:92-130) for the segments that are past 20 seeds, one after the other, the wave voting over the 21
-                    unsigned long long need = __ballot(ev && newscore > RF_SM);
-                    while (need) {
-                        const int src = __ffsll((long long)need) - 1;
-                        need &= need - 1;
-                        rf_sync();
-                        vshort* r = rec(__shfl(seg, src));
-                        const int noff = __shfl(off, src);
-                        if (lane < RF_SM) { S.tl[lane] = r[R_LOC + lane]; S.ts[lane] = r[R_SEED + lane]; }
-                        if (lane == RF_SM) { S.tl[lane] = noff; S.ts[lane] = k + 1; }
-                        S.tsc[lane] = 0;
-                        __builtin_amdgcn_wave_barrier();
-                        rf_vote<true>(S, RF_SM + 1, lane, bcf, cutoff, 0x7fffffff);
-                        int minval = 10000, mini = -1;                 // (the first entry with the fewest votes)
-                        for (int j = 0; j <= RF_SM; ++j) {
-                            const int v = S.tsc[j];
-                            if (minval > v) { minval = v; mini = j; }
-                        }
-                        if (minval == RF_SM) {
-                            if (lane == 0) { r[R_LOC + RF_SM - 1] = (short)noff; r[R_SEED + RF_SM - 1] = (short)(k + 1); }
-                        } else if (minval < RF_SM && mini < RF_SM) {
-                            if (lane >= mini && lane < RF_SM) { r[R_LOC + lane] = (short)S.tl[lane + 1]; r[R_SEED + lane] = (short)S.ts[lane + 1]; }
-                            if (lane == src) { --newscore; r[R_SCORE] = (short)newscore; }
-                        }
-                        __builtin_amdgcn_wave_barrier();
-                    }
-                    rf_sync();
-                    int idx = 0;
-                    if (ev) idx = rf_index(rec(seg));
-                    const unsigned long long fresh = __ballot(ev && idx == -1);
-                    if (ev) {
-                        const int sk = seg > 0 ? newscore + (int)rec(seg - 1)[R_SCORE] : newscore;      // :438-439
-                        if (idx == -1) {
-                            const int t = touched + (int)__popcll(fresh & below);
-                            ilist[t] = seg;
-                            iscore[t] = (short)sk;
-                            rf_set_index(rec(seg), t);
-                        } else iscore[idx] = (short)sk;
-                    }
-                    touched += (int)__popcll(fresh);
-                    rf_sync();
-                }
-                if (ovf) break;
-                s0 = n0; s1 = n1; pfirst = pnext;
-                n0 = m0; n1 = m1;
-            }
+            // ---- seeding (:417-453): ref_seed_dev.h
+            ovf = !rf_seed_strand(W, S, starts, offsets, qpac, qnpac, qoff, L, K, bcq, bcf, Z, strand, cutoff, lane, touched);
             // ---- candidates (:456-561)
             for (int i = 0; i < touched && !ovf; ++i) {
                 const int seg = ((volatile int*)ilist)[i];
@@ -265,31 +92,8 @@ __global__ __launch_bounds__(RF_BLOCK) void ref_seed(const uint32_t* __restrict_
                 S.tsc[lane] = 0;
                 __builtin_amdgcn_wave_barrier();
                 rf_vote<false>(S, nl, lane, bcf, cutoff, L);
-                int flag = 0, rep_loc = 0, loc0 = 0, loc1 = 0;
-                {
-                    int maxval = 0, maxi = 0, rep = 0;
-                    for (int j = 0; j < nl; ++j) {
-                        const int v = S.tsc[j];
-                        if (maxval < v) { maxval = v; maxi = j; rep = 0; }
-                        else if (maxval == v) ++rep;
-                    }
-                    if (maxval >= 5 && rep == maxval) { flag = 1; loc0 = S.tl[maxi]; loc1 = S.ts[maxi]; rep_loc = maxi; }
-                    else if (maxval >= 5) {
-                        // the entries that agree with the best one, in index order (before it, itself, after it): each is taken as the start
-                        // point while none is held — "none" is `loc[0] == 0` in the reference (mecat2ref_aux.cpp:40-79)
-                        flag = 1;
-                        const int lm = S.tl[maxi], sm = S.ts[maxi];
-                        for (int j = 0; j < maxi; ++j) {
-                            const int lj = S.tl[j], sj = S.ts[j];
-                            if (sm - sj > 0 && lm - lj > 0 && lm - lj < L && rf_ddf<false>(lm - lj, sm - sj, bcf, cutoff) && loc0 == 0) { loc0 = lj; loc1 = sj; rep_loc = j; }
-                        }
-                        if (loc0 == 0) { loc0 = lm; loc1 = sm; rep_loc = maxi; }
-                        for (int j = maxi + 1; j < nl; ++j) {
-                            const int lj = S.tl[j], sj = S.ts[j];
-                            if (sj - sm > 0 && lj - lm > 0 && lj - lm <= L && rf_ddf<false>(lj - lm, sj - sm, bcf, cutoff) && loc0 == 0) { loc0 = lj; loc1 = sj; rep_loc = j; }
-                        }
-                    }
-                }
+                int rep_loc, loc0, loc1;
+                const bool flag = rf_select(S, nl, L, bcf, cutoff, loc0, loc1, rep_loc);
                 if (!flag) continue;
                 const int vote = S.tsc[rep_loc];
                 if (vote < 6) continue;                                  // :496
@@ -357,27 +161,19 @@ __global__ __launch_bounds__(RF_BLOCK) void ref_seed(const uint32_t* __restrict_
                 if (ncand < maxc) ++ncand;
                 __builtin_amdgcn_wave_barrier();
             }
-            // ---- the strand is done (or given up): its records go back to the untouched state (one contiguous stretch of the pool) and their
-            // segments' directory entries to 0
-            {
-                volatile uint32_t* w = (volatile uint32_t*)(pool + RF_REC);         // (RF_REC shorts = 22 words per record)
-                const int nw = (nslots - 1) * (RF_REC / 2);
-                for (int j = lane; j < nw; j += 64) w[j] = (j % (RF_REC / 2)) == (RF_REC / 2 - 1) ? 0xffffffffu : 0u;
-                for (int sl = 1 + lane; sl < nslots; sl += 64) dir[slotseg[sl]] = 0u;
-                nslots = 1;
-            }
-            rf_sync();
+            // ---- the strand is done (or given up): its records go back to the pool
+            W.release(lane);
         }
         if (ovf) ncand = 0;
         for (int j = lane; j < ncand; j += 64) out[uo * (size_t)maxc + j] = S.cand[j];
         if (lane == 0) {
             out_counts[uo] = ovf ? -1 : ncand;
-            atomicMax(cursor + 4, (unsigned int)hw);
+            atomicMax(cursor + 4, (unsigned int)W.hw);
             if (ovf) atomicAdd(cursor + 5, 1u);
         }
         rf_sync();
     }
-    if (lane == 0) hw_all[gw] = hw;
+    if (lane == 0) hw_all[gw] = W.hw;
 }
 
 int64_t g_last_stats[4] = {0, 0, 0, 0};
@@ -401,35 +197,13 @@ int ref_seed_run(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref, con
     if (n == 0) return 0;
     const int Z = p->round ? 2000 : 1000, gate = p->round ? 4 : 6;
     const int nseg = ref->num_bases / Z + 5;
-    // One directory + record pool per resident wave, 12 waves per CU (the kernel's registers allow 3 per SIMD), fewer when they would
-    // take more than half of the free memory.  MECAT_REF_POOL overrides the pool's records (the test of the second launch makes it small).
-    const char* pe = getenv("MECAT_REF_POOL");
-    const int pcap = std::min(nseg + 1, std::max(8, pe && atoi(pe) > 0 ? atoi(pe) : RF_POOL));
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const size_t rec_bytes = RF_REC * sizeof(short) + sizeof(int) + sizeof(short) + sizeof(int);
-    const size_t per_wave = (size_t)pcap * rec_bytes + (size_t)(nseg + 8) * sizeof(uint32_t);
-    const size_t max_waves = (size_t)c->num_cus * 12;
-    size_t waves = std::min<size_t>(max_waves, std::max<size_t>(1, free_b / 2 / per_wave));
-    waves = std::min<size_t>(waves, (size_t)n);
-    const unsigned grid = (unsigned)((waves + RF_WAVES - 1) / RF_WAVES);
-    waves = (size_t)grid * RF_WAVES;
-    short *d_pool, *d_iscore;
-    uint32_t* d_dir;
-    int *d_ilist, *d_slotseg, *d_hw;
-    unsigned int* d_cur;
-    if (c->scratch("rf_pool", sizeof(short) * waves * (size_t)pcap * RF_REC, (void**)&d_pool)) return -1;
-    if (c->scratch("rf_dir", sizeof(uint32_t) * waves * (size_t)(nseg + 8), (void**)&d_dir)) return -1;
-    if (c->scratch("rf_hw", sizeof(int) * waves, (void**)&d_hw)) return -1;
-    if (c->scratch("rf_ilist", sizeof(int) * waves * (size_t)pcap, (void**)&d_ilist)) return -1;
-    if (c->scratch("rf_iscore", sizeof(short) * waves * (size_t)pcap, (void**)&d_iscore)) return -1;
-    if (c->scratch("rf_slotseg", sizeof(int) * waves * (size_t)pcap, (void**)&d_slotseg)) return -1;
-    if (c->scratch("rf_cursor", 64, (void**)&d_cur)) return -1;
-    HIPCHK(hipMemsetAsync(d_dir, 0, sizeof(uint32_t) * waves * (size_t)(nseg + 8), c->stream));
-    HIPCHK(hipMemsetAsync(d_hw, 0, sizeof(int) * waves, c->stream));        // (the pools count as uninitialised: records are set up as they are handed out)
-    HIPCHK(hipMemsetAsync(d_cur, 0, 64, c->stream));
-    LAUNCH(c, "ref_seed", ref_seed, grid, RF_BLOCK, 0, (const uint32_t*)idx->d_starts, (const int32_t*)idx->d_offsets, (const uint32_t*)reads->d_pac,
-           (const uint32_t*)reads->d_npac, (const mhip_offset_t*)reads->d_offs, rid_begin, n, (const int*)nullptr, d_pool, d_dir, d_hw, d_ilist, d_iscore, d_slotseg,
+    RfPools P;
+    if (rf_pools_first(c, nseg, n, &P)) return -1;
+    const size_t waves = P.waves;
+    const int pcap = P.pcap;
+    unsigned int* d_cur = P.cur;
+    LAUNCH(c, "ref_seed", ref_seed, P.grid, RF_BLOCK, 0, (const uint32_t*)idx->d_starts, (const int32_t*)idx->d_offsets, (const uint32_t*)reads->d_pac,
+           (const uint32_t*)reads->d_npac, (const mhip_offset_t*)reads->d_offs, rid_begin, n, (const int*)nullptr, P.pool, P.dir, P.hw, P.ilist, P.iscore, P.slotseg,
            nseg, pcap, Z, p->round, gate, p->ddfs_cutoff, ref->num_bases, p->maxc, d_cur, d_out, d_cnt);
     HIPCHK(hipGetLastError());
     unsigned int st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -446,25 +220,14 @@ int ref_seed_run(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref, con
         std::vector<int> redo;
         for (int i = 0; i < n; ++i)
             if (cnt[i] < 0) redo.push_back(rid_begin + i);
-        const int full = nseg + 1;
-        size_t w2 = std::min<size_t>(std::min<size_t>(waves, redo.size()), std::max<size_t>(1, free_b / 4 / ((size_t)full * rec_bytes)));
-        const unsigned grid2 = (unsigned)((w2 + RF_WAVES - 1) / RF_WAVES);
-        w2 = (size_t)grid2 * RF_WAVES;
-        if (w2 > waves) { mhip_set_error("ref_seed: no room for the worst-case pools of %zu reads", redo.size()); return -1; }
-        short *d_pool2, *d_iscore2;
-        int *d_ilist2, *d_slotseg2, *d_redo, *d_hw2;
-        if (c->scratch("rf_pool_full", sizeof(short) * w2 * (size_t)full * RF_REC, (void**)&d_pool2)) return -1;
-        if (c->scratch("rf_ilist_full", sizeof(int) * w2 * (size_t)full, (void**)&d_ilist2)) return -1;
-        if (c->scratch("rf_iscore_full", sizeof(short) * w2 * (size_t)full, (void**)&d_iscore2)) return -1;
-        if (c->scratch("rf_slotseg_full", sizeof(int) * w2 * (size_t)full, (void**)&d_slotseg2)) return -1;
-        if (c->scratch("rf_hw_full", sizeof(int) * w2, (void**)&d_hw2)) return -1;
+        RfPools F;
+        int* d_redo;
+        if (rf_pools_full(c, P, redo.size(), "ref_seed", &F)) return -1;
         if (c->scratch("rf_redo", sizeof(int) * redo.size(), (void**)&d_redo)) return -1;
-        HIPCHK(hipMemsetAsync(d_hw2, 0, sizeof(int) * w2, c->stream));
-        HIPCHK(hipMemsetAsync(d_cur, 0, 64, c->stream));
         HIPCHK(hipMemcpyAsync(d_redo, redo.data(), sizeof(int) * redo.size(), hipMemcpyHostToDevice, c->stream));
-        LAUNCH(c, "ref_seed_full", ref_seed, grid2, RF_BLOCK, 0, (const uint32_t*)idx->d_starts, (const int32_t*)idx->d_offsets, (const uint32_t*)reads->d_pac,
-               (const uint32_t*)reads->d_npac, (const mhip_offset_t*)reads->d_offs, rid_begin, (int)redo.size(), (const int*)d_redo, d_pool2, d_dir, d_hw2, d_ilist2,
-               d_iscore2, d_slotseg2, nseg, full, Z, p->round, gate, p->ddfs_cutoff, ref->num_bases, p->maxc, d_cur, d_out, d_cnt);
+        LAUNCH(c, "ref_seed_full", ref_seed, F.grid, RF_BLOCK, 0, (const uint32_t*)idx->d_starts, (const int32_t*)idx->d_offsets, (const uint32_t*)reads->d_pac,
+               (const uint32_t*)reads->d_npac, (const mhip_offset_t*)reads->d_offs, rid_begin, (int)redo.size(), (const int*)d_redo, F.pool, F.dir, F.hw, F.ilist,
+               F.iscore, F.slotseg, nseg, F.pcap, Z, p->round, gate, p->ddfs_cutoff, ref->num_bases, p->maxc, d_cur, d_out, d_cnt);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(c->stream));          // (`redo` is read by the copy above until here)
     }

@@ -448,6 +448,104 @@ def ref_extend_stats():
     return dict(slots=int(v[0]), slices=int(v[1]), row_bytes=int(v[2]), store_words=int(v[3]))
 
 
+class RefRescueParams(C.Structure):      # mhip_ref_rescue_params
+    _fields_ = [("maxc", C.c_int32), ("round", C.c_int32), ("num_output", C.c_int32), ("tech", C.c_int32), ("ddfs_cutoff", C.c_double)]
+
+
+# mhip_ref_rescue_state: what rescue_clipped_align holds when it starts to look for rescue candidates (mecat2ref_aux.cpp:328-341)
+REF_RESCUE_STATE_DTYPE = np.dtype([("naln", np.int32), ("go_on", np.int32), ("nres", np.int32), ("qs", np.int32), ("slot", np.int8, 16), ("id", np.int8, 16)])
+REF_RESCUE_TRIES = 6
+assert REF_RESCUE_STATE_DTYPE.itemsize == 48 and C.sizeof(RefRescueParams) == 24
+
+
+def ref_rescue_params(tech=0, **kw):
+    """mhip_ref_rescue_params_default, then the given members"""
+    p = RefRescueParams()
+    lib().mhip_ref_rescue_params_default.argtypes = [C.POINTER(RefRescueParams), C.c_int]
+    lib().mhip_ref_rescue_params_default.restype = None
+    lib().mhip_ref_rescue_params_default(C.byref(p), tech)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+_REF_RESCUE_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(RefRescueParams), C.c_void_p, C.POINTER(C.c_int64)]
+
+
+def ref_rescue_run(ctx, idx, ref, reads, rid_begin, rid_end, params, res):
+    """mhip_ref_rescue_run: mecat2ref's rescue and result order on host results res [n, maxc] (ref_extend_fetch's) -> total words of
+    the rescue results"""
+    res = np.ascontiguousarray(res, dtype=REF_RESULT_DTYPE)
+    assert res.shape == (max(rid_end - rid_begin, 0), params.maxc)
+    tot = C.c_int64()
+    lib().mhip_ref_rescue_run.argtypes = _REF_RESCUE_ARGS
+    _chk(lib().mhip_ref_rescue_run(ctx.h, idx.h, ref.h, reads.h, rid_begin, rid_end, C.byref(params), res.ctypes.data, C.byref(tot)))
+    return tot.value
+
+
+def ref_rescue_run_dev(ctx, idx, ref, reads, rid_begin, rid_end, params, d_res=None):
+    """mhip_ref_rescue_run_dev: the same on device results; None = those of the last ref_extend_run* on this context"""
+    tot = C.c_int64()
+    lib().mhip_ref_rescue_run_dev.argtypes = _REF_RESCUE_ARGS
+    _chk(lib().mhip_ref_rescue_run_dev(ctx.h, idx.h, ref.h, reads.h, rid_begin, rid_end, C.byref(params), d_res, C.byref(tot)))
+    return tot.value
+
+
+def ref_rescue_fetch(ctx, n, num_output, total_words):
+    """mhip_ref_rescue_fetch -> dict(out_slots int32[n, 3 * num_output], out_counts, cands [n, 6] REF_CAND_DTYPE, counts, res [n, 6]
+    REF_RESULT_DTYPE, word_offs uint64[6 n + 1], words); candidates and results behind a read's count are zeroed"""
+    T = REF_RESCUE_TRIES
+    slots = np.full((n, 3 * num_output), -1, dtype=np.int32)
+    oc, cnt = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    cands = np.zeros((n, T), dtype=REF_CAND_DTYPE)
+    res = np.zeros((n, T), dtype=REF_RESULT_DTYPE)
+    offs = np.zeros(n * T + 1, dtype=np.uint64)
+    words = np.zeros(max(total_words, 1), dtype=np.uint32)
+    lib().mhip_ref_rescue_fetch.argtypes = [C.c_void_p] * 8
+    _chk(lib().mhip_ref_rescue_fetch(ctx.h, slots.ctypes.data, oc.ctypes.data, cands.ctypes.data, cnt.ctypes.data, res.ctypes.data, offs.ctypes.data, words.ctypes.data))
+    behind = np.arange(T)[None, :] >= cnt[:, None]
+    cands[behind] = np.zeros((), dtype=REF_CAND_DTYPE)
+    return dict(out_slots=slots, out_counts=oc, cands=cands, counts=cnt, res=res, word_offs=offs, words=words[:total_words])
+
+
+def ref_rescue_stats():
+    """mhip_ref_rescue_stats of the last run: dict(reads, went_on, candidates, redone)"""
+    v = (C.c_int64 * 4)()
+    lib().mhip_ref_rescue_stats.restype = None
+    lib().mhip_ref_rescue_stats(v)
+    return dict(reads=int(v[0]), went_on=int(v[1]), candidates=int(v[2]), redone=int(v[3]))
+
+
+def debug_ref_rescue_prep(ctx, params, res):
+    """test hook: ref_rescue_prep (the sort, the containment filter and the full-alignment test of rescue_clipped_align) on host
+    results res [n, maxc] REF_RESULT_DTYPE -> states [n] REF_RESCUE_STATE_DTYPE"""
+    res = np.ascontiguousarray(res, dtype=REF_RESULT_DTYPE)
+    assert res.ndim == 2 and res.shape[1] == params.maxc
+    st = np.zeros(len(res), dtype=REF_RESCUE_STATE_DTYPE)
+    lib().mhip_debug_ref_rescue_prep.argtypes = [C.c_void_p, C.POINTER(RefRescueParams), C.c_int, C.c_void_p, C.c_void_p]
+    _chk(lib().mhip_debug_ref_rescue_prep(ctx.h, C.byref(params), len(res), res.ctypes.data, st.ctypes.data))
+    return st
+
+
+def debug_ref_rescue_finish(ctx, params, res, states, rescue_counts, rescue_meta, rescue_res):
+    """test hook: ref_rescue_finish (the attach tests, the second sort with its cut and output_results) on hand-made states and rescue
+    results.  rescue_meta int32[n, 6] = owner entry | side << 8, rescue_res [n, 6] REF_RESULT_DTYPE
+    -> (out_slots int32[n, 3 * num_output], out_counts int32[n])"""
+    res = np.ascontiguousarray(res, dtype=REF_RESULT_DTYPE)
+    st = np.ascontiguousarray(states, dtype=REF_RESCUE_STATE_DTYPE)
+    cnt = np.ascontiguousarray(rescue_counts, dtype=np.int32)
+    meta = np.ascontiguousarray(rescue_meta, dtype=np.int32)
+    rres = np.ascontiguousarray(rescue_res, dtype=REF_RESULT_DTYPE)
+    n = len(st)
+    assert res.shape == (n, params.maxc) and cnt.shape == (n,) and meta.shape == (n, REF_RESCUE_TRIES) and rres.shape == (n, REF_RESCUE_TRIES)
+    slots = np.zeros((n, 3 * max(params.num_output, 1)), dtype=np.int32)
+    oc = np.zeros(n, dtype=np.int32)
+    lib().mhip_debug_ref_rescue_finish.argtypes = [C.c_void_p, C.POINTER(RefRescueParams), C.c_int] + [C.c_void_p] * 7
+    _chk(lib().mhip_debug_ref_rescue_finish(ctx.h, C.byref(params), n, res.ctypes.data, st.ctypes.data, cnt.ctypes.data, meta.ctypes.data, rres.ctypes.data,
+                                            slots.ctypes.data, oc.ctypes.data))
+    return slots, oc
+
+
 def asm_jobs_from_candidates(cands, counts, rid_begin=0):
     """the (candidate, both directions) jobs of an asm_seed_reads table, read by read in list order (include/mecat_hip.h: x0 = loc1 - 1 -
     readstart; left from (x0 + 12, loc2 + 12) with left1 / left2 bases, right from (x0, loc2) with right1 / right2) -> [n] ASM_JOB_DTYPE"""

@@ -49,3 +49,18 @@ RefAlignInfo ref_result_align_info(const mhip_ref_result& r, int id) {
     a.prev_id = a.next_id = a.parent_id = -1;
     return a;
 }
+
+bool ref_read_records(int read_id, const int32_t* out_slots, int out_count, const RefResultSet& first, const RefResultSet& rescue,
+                      const uint8_t* reads_pac, const uint8_t* reads_nplane, int64_t read_off, const uint8_t* ref_pac, std::string* out) {
+    out->clear();
+    std::string qmap, smap;
+    for (int i = 0; i < out_count; ++i) {
+        const int s = out_slots[i];
+        const RefResultSet& set = s < first.count ? first : rescue;
+        const int k = s < first.count ? s : s - first.count;
+        if (k < 0 || k >= set.count || !set.res[k].ok) return false;
+        if (!ref_result_strings(set.res[k], set.words + set.offs[k], reads_pac, reads_nplane, read_off, ref_pac, &qmap, &smap)) return false;
+        *out += ref_result_record(read_id, set.res[k], qmap, smap);
+    }
+    return true;
+}
