@@ -336,8 +336,8 @@ void mhip_ref_seed_stats(int64_t out[4]);
  * (mecat_amd/host/ref_results.h rebuilds the text).  Empty slots and results with ok = 0 take zero words.
  * mhip_ref_extend_run extends the batch, leaves everything on the device and returns the words the ok results take;
  * mhip_ref_extend_fetch — same context, before the next _run — copies out res[n * maxc], word_offs[n * maxc + 1] (result s occupies words
- * [word_offs[s], word_offs[s + 1]) of ops_dense) and the words.  Refused with a message (-1): tech != 0 (nanopore mode needs the X-drop
- * aligner's strings, not built), a read of 100 000 letters or more (RM), a candidate whose loc1 or loc2 lies outside the reference or
+ * [word_offs[s], word_offs[s + 1]) of ops_dense) and the words.  Refused with a message (-1): tech != 0 (nanopore mode has calls of its
+ * own, mhip_ref_xextend_run below), a read of 100 000 letters or more (RM), a candidate whose loc1 or loc2 lies outside the reference or
  * the read (nothing is extended then). */
 typedef struct { int32_t ok, chain, vscore, qb, qe, qs; int64_t sb, se; int32_t cols, pad; } mhip_ref_result;   /* TempResult without its strings, mecat2ref_defs.h */
 int  mhip_ref_extend_run(mhip_ctx* ctx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, int maxc, int tech,
@@ -348,6 +348,23 @@ int  mhip_ref_extend_run_dev(mhip_ctx* ctx, const mhip_volume* ref, const mhip_v
 int  mhip_ref_extend_fetch(mhip_ctx* ctx, mhip_ref_result* res /*[n][maxc]*/, uint64_t* word_offs /*[n * maxc + 1]*/, uint32_t* ops_dense /*[total_words]*/);
 /* measurement hook: of the last mhip_ref_extend_run* call — [0] slots, [1] slices, [2] bytes of row scratch, [3] words of the column store */
 void mhip_ref_extend_stats(int64_t out[4]);
+
+/* ---- mecat2ref, stage 2 in nanopore mode (`-x 1`): the same candidates through XdropAligner::go, with the aligned strings ----
+ * The technology changes one thing in the tool: reference_mapping creates an XdropAligner instead of a DiffAligner
+ * (mecat2ref_impl_large.cpp:328-335).  Same arguments as mhip_ref_extend_run* without `tech`, the same jobs, windows, strand rule, slices
+ * and refusals; the results go to the same buffers, so mhip_ref_extend_fetch fetches them.  What differs (common/xdrop_gapalign.cpp:
+ * 263-439): the blocks are affine X-drop extensions (reward 1, penalty -1, gap 0 / 1, X = 30), the left half is joined without its last
+ * column (:401-402), and ok = qe - qb >= 1000 — the QUERY SPAN (:438), not the columns: a result with 1000 columns and a shorter span
+ * is not ok, cols = aln_size either way.  X-drop paths hold substitutions over unequal bases: a column of code 0 takes a base of each
+ * sequence and the two may differ (mismatch columns); mecat_amd/host/ref_results.h writes the letters, which tell them apart.
+ * MECAT_XD_WIDE=1 (read at call time) sends every block through the wide block: the ring block's cross-check. */
+int  mhip_ref_xextend_run(mhip_ctx* ctx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, int maxc,
+                          const mhip_ref_candidate* cands /*[n][maxc]*/, const int32_t* counts, int64_t* total_words);
+int  mhip_ref_xextend_run_dev(mhip_ctx* ctx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, int maxc,
+                              const mhip_ref_candidate* d_cands, const int32_t* d_counts, int64_t* total_words);
+/* measurement hook: of the last mhip_ref_xextend_run* call — [0] slots, [1] slices, [2] blocks redone with the wide block (their window
+ * outgrew the ring block's 128 cells: low-complexity sequence), [3] words of the column store */
+void mhip_ref_xextend_stats(int64_t out[4]);
 
 /* ---- mecat2ref, stage 3: the clipped-alignment rescue and the result order (PacBio mode) ----
  * Replaces everything of reference_mapping between its extension loop and the per-thread result file (mecat2ref_impl_large.cpp:584-603
@@ -364,7 +381,7 @@ void mhip_ref_extend_stats(int64_t out[4]);
  * mhip_ref_rescue_state, what :328-341 leave: naln surviving entries in the sorted order, entry k = list slot slot[k] with the tool's id
  * id[k] (its index among the read's ok results); nres = ok results of the first list (the id the first ok rescue result takes); qs = the
  * read's length; go_on = 0 when the tool returns at :341 (the longest entry covers 0.9 of the read) or there is no entry.
- * Refused with a message and -1, the context stays usable: tech != 0, maxc outside 1..10 (std::sort's order of equal lengths is
+ * Refused with a message and -1, the context stays usable: tech != 0 (nanopore mode: mhip_ref_xrescue_run), maxc outside 1..10 (std::sort's order of equal lengths is
  * reproduced for at most 16 entries), num_output < 1, round outside 0..1, a read of 100 000 letters or more, an index that was not
  * built from this reference. */
 typedef struct { int32_t maxc, round, num_output, tech; double ddfs_cutoff; } mhip_ref_rescue_params;
@@ -378,6 +395,14 @@ int  mhip_ref_rescue_run(mhip_ctx* ctx, const mhip_index* idx, const mhip_volume
  * are not n * maxc) */
 int  mhip_ref_rescue_run_dev(mhip_ctx* ctx, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end,
                              const mhip_ref_rescue_params* params, const mhip_ref_result* d_res, int64_t* total_words);
+/* Nanopore mode: stage 3 with the X-drop extension (mhip_ref_xextend_run's) behind the rescue candidates.  Prep, the searches, the
+ * re-seeding, the attach tests and the output order do not depend on the technology; the extension and its ok rule do.  params->tech
+ * must be 1 (as mhip_ref_rescue_run wants 0: a caller that mixes the two up is told); the other refusals are the PacBio calls'.
+ * Results are fetched by mhip_ref_rescue_fetch. */
+int  mhip_ref_xrescue_run(mhip_ctx* ctx, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end,
+                          const mhip_ref_rescue_params* params, const mhip_ref_result* res /*[n][maxc]*/, int64_t* total_words);
+int  mhip_ref_xrescue_run_dev(mhip_ctx* ctx, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end,
+                              const mhip_ref_rescue_params* params, const mhip_ref_result* d_res, int64_t* total_words);
 /* same context, before the next mhip_ref_rescue_run*: rescue_cands / rescue_res [n][6] (entries behind rescue_counts[i] are undefined),
  * word_offs[6 n + 1] and ops_dense[total_words] as mhip_ref_extend_fetch gives them for the rescue results */
 int  mhip_ref_rescue_fetch(mhip_ctx* ctx, int32_t* out_slots /*[n][3 * num_output]*/, int32_t* out_counts, mhip_ref_candidate* rescue_cands,

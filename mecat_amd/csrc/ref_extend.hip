@@ -1,5 +1,6 @@
 // ref_extend.hip — mecat2ref, stage 2: every listed candidate through DiffAligner::go on the device, with the two
-// aligned strings as 2-bit columns.  PacBio mode only (the tool's default `-x 0`).
+// aligned strings as 2-bit columns.  PacBio mode (the tool's default `-x 0`); in nanopore mode the same jobs, bounds, slices, stitch and
+// join run around ref_xextend.hip's kernel (ref_extend_run's `aligner`).
 //
 // Replaces the extend_candidate loop of reference_mapping (mecat2ref/mecat2ref_impl_large.cpp:566-582 for round 1, :829-845 for round 2):
 //   extend_candidate         mecat2ref/mecat2ref_aux.cpp:123-183    the job, go, the result's coordinates
@@ -53,14 +54,6 @@
 #define RX_GROW ((size_t)RX_MAX_D * RX_ROW_W)
 #define RX_RM 100000             // the tool's read buffers (RM, mecat2ref_defs.h)
 #define RX_MIN_COLS 1000         // extend_candidate's min_aln_size (mecat2ref_aux.cpp:152)
-
-struct RxJob {
-    int64_t ref_start;           // loc1 - 1
-    int32_t rid, chain, read_start, read_len;
-    int32_t left, right;         // left_ref_size, right_ref_size
-    int32_t valid, score;
-};
-struct RxDir { int32_t cols, qbases, tbases, blocks; };
 
 struct RxLds {
     uint32_t Qp[RX_SEQ_WORDS];
@@ -373,7 +366,8 @@ __global__ __launch_bounds__(RX_BLOCK, 4) void ref_extend(const uint32_t* __rest
 
 // ---------------------------------------------------------------- stitch and join
 // go's coordinates (:324-325, :343-344), extend_candidate's sb / se (:161-162); words[s] = the words result s takes in the dense output
-__global__ __launch_bounds__(256) void ref_stitch(const RxJob* __restrict__ jobs, const RxDir* __restrict__ dres, int s0, int s1,
+// xdrop: XdropAligner::go's rule (xdrop_gapalign.cpp:438), ok = the query span >= 1000, not the columns; cols = aln_size either way
+__global__ __launch_bounds__(256) void ref_stitch(const RxJob* __restrict__ jobs, const RxDir* __restrict__ dres, int s0, int s1, int xdrop,
                                                   mhip_ref_result* __restrict__ res, uint32_t* __restrict__ words,
                                                   unsigned long long* __restrict__ counters) {
     const int s = s0 + blockIdx.x * 256 + threadIdx.x;
@@ -384,9 +378,9 @@ __global__ __launch_bounds__(256) void ref_stitch(const RxJob* __restrict__ jobs
     if (j.valid) {
         const RxDir L = dres[2 * s], R = dres[2 * s + 1];
         r.cols = L.cols + R.cols;
-        r.ok = r.cols >= RX_MIN_COLS;
         r.chain = j.chain; r.vscore = j.score;
         r.qb = j.read_start - L.qbases; r.qe = j.read_start + R.qbases; r.qs = j.read_len;
+        r.ok = xdrop ? r.qe - r.qb >= RX_MIN_COLS : r.cols >= RX_MIN_COLS;
         r.sb = j.ref_start - L.tbases; r.se = j.ref_start + R.tbases;      // ref_start - left + (left -/+ bases)
         w = r.ok ? (uint32_t)((r.cols + 15) >> 4) : 0u;
         if (r.ok) {                                  // the work counters dw_stitch keeps (align.hip)
@@ -422,19 +416,19 @@ __global__ __launch_bounds__(256) void ref_join(const mhip_ref_result* __restric
 }
 
 int64_t g_last_stats[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};      // of the last run into each buffer set: jobs, slices, bytes of row scratch, words of the column store
+int64_t g_last_xstats[4] = {0, 0, 0, 0};                         // of the last X-drop run into set 0: jobs, slices, blocks redone with the wide block, words of the column store
 
 }  // namespace
 
 // Results, word offsets and dense words go to buffer set `set` (ref_extend.h) and stay there until the next run into the same set;
 // everything else is working memory shared by the sets.
-int ref_extend_run(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, int maxc, int tech,
+int ref_extend_run(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, int maxc, int aligner,
                    const mhip_ref_candidate* d_cands, const int32_t* d_counts, int64_t* total_words, int set) {
     c->rx_slots[set] = 0; c->rx_total[set] = 0; c->rx_on_host[set] = false;
     if (total_words) *total_words = 0;
-    if (tech != 0) {
-        mhip_set_error("mhip_ref_extend_run: tech = %d: only PacBio mode (tech 0, DiffAligner) is built; nanopore mode needs the X-drop aligner's aligned strings", tech);
-        return -1;
-    }
+    if (aligner != RX_ALIGNER_DIFF && aligner != RX_ALIGNER_XDROP) { mhip_set_error("mhip_ref_extend_run: aligner %d", aligner); return -1; }
+    const bool xdrop = aligner == RX_ALIGNER_XDROP;
+    if (xdrop && set == 0) for (int i = 0; i < 4; ++i) g_last_xstats[i] = 0;
     if (rid_begin < 0 || rid_end < rid_begin || rid_end > reads->num_reads) { mhip_set_error("mhip_ref_extend_run: bad read range [%d, %d) of %d", rid_begin, rid_end, reads->num_reads); return -1; }
     if (maxc < 1 || maxc > 100) { mhip_set_error("mhip_ref_extend_run: list length %d outside [1, 100]", maxc); return -1; }
     for (int r = rid_begin; r < rid_end; ++r)
@@ -504,9 +498,9 @@ int ref_extend_run(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads
     // an ok result's words are no more than its two directions' bounds: the dense output of a slice fits what its store takes
     if (scratch_set(c, "rx_dense", set, sizeof(uint32_t) * (size_t)(store_words + 1), (void**)&d_dense)) return -1;
     const int max_waves = c->num_cus * 16;               // 4 waves per SIMD, as dw_extend; LDS 5.6 KB per wave
-    uint16_t* d_g;
-    if (c->scratch("rx_rows", sizeof(uint16_t) * RX_GROW * (size_t)max_waves, (void**)&d_g)) return -1;
-    g_last_stats[set][0] = slots; g_last_stats[set][1] = nslices; g_last_stats[set][2] = (int64_t)(sizeof(uint16_t) * RX_GROW * (size_t)max_waves);
+    uint16_t* d_g = nullptr;
+    if (!xdrop && c->scratch("rx_rows", sizeof(uint16_t) * RX_GROW * (size_t)max_waves, (void**)&d_g)) return -1;
+    g_last_stats[set][0] = slots; g_last_stats[set][1] = nslices; g_last_stats[set][2] = xdrop ? 0 : (int64_t)(sizeof(uint16_t) * RX_GROW * (size_t)max_waves);
     g_last_stats[set][3] = (int64_t)store_words;
     if (nslices > 1) c->rx_words[set].clear();
     unsigned long long wbase = 0;
@@ -516,10 +510,13 @@ int ref_extend_run(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads
         const int grid = std::max(1, std::min(max_waves / RX_WAVES, (int)((u1 - u0 + RX_WAVES - 1) / RX_WAVES)));
         HIPCHK(hipMemsetAsync(d_store, 0, sizeof(uint32_t) * (size_t)(store_words + 1), c->stream));
         HIPCHK(hipMemsetAsync(d_cur, 0, sizeof(unsigned int), c->stream));
-        LAUNCH(c, "ref_extend", ref_extend, grid, RX_BLOCK, 0, (const uint32_t*)ref->d_pac, (const uint32_t*)reads->d_pac, (const uint32_t*)reads->d_npac,
-               (const mhip_offset_t*)reads->d_offs, (const RxJob*)d_jobs, u0, u1, (const unsigned long long*)d_dbase, d_store, d_dres, d_g, d_cur,
-               (unsigned long long*)c->d_counters);
-        LAUNCH(c, "ref_stitch", ref_stitch, (s1 - s0 + 255) / 256, 256, 0, (const RxJob*)d_jobs, (const RxDir*)d_dres, s0, s1, d_res, d_rwords,
+        if (xdrop) {                                     // (d_cur + 12 counts the blocks redone with the wide block, over the slices)
+            if (ref_xextend_launch(c, ref, reads, d_jobs, u0, u1, d_dbase, d_store, d_dres, d_cur, d_cur + 12)) return -1;
+        } else
+            LAUNCH(c, "ref_extend", ref_extend, grid, RX_BLOCK, 0, (const uint32_t*)ref->d_pac, (const uint32_t*)reads->d_pac, (const uint32_t*)reads->d_npac,
+                   (const mhip_offset_t*)reads->d_offs, (const RxJob*)d_jobs, u0, u1, (const unsigned long long*)d_dbase, d_store, d_dres, d_g, d_cur,
+                   (unsigned long long*)c->d_counters);
+        LAUNCH(c, "ref_stitch", ref_stitch, (s1 - s0 + 255) / 256, 256, 0, (const RxJob*)d_jobs, (const RxDir*)d_dres, s0, s1, xdrop ? 1 : 0, d_res, d_rwords,
                (unsigned long long*)c->d_counters);
         LAUNCH(c, "ref_scan", ref_scan, 1, 1024, 0, (const uint32_t*)d_rwords, (long long)(s1 - s0), wbase, d_swoffs);
         LAUNCH(c, "ref_join", ref_join, s1 - s0, 256, 0, (const mhip_ref_result*)d_res, (const RxDir*)d_dres, s0, s1, (const unsigned long long*)d_dbase, u0,
@@ -535,6 +532,11 @@ int ref_extend_run(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads
             if (wend > wbase) HIPCHK(hipMemcpy(c->rx_words[set].data() + wbase, d_dense, sizeof(uint32_t) * (size_t)(wend - wbase), hipMemcpyDeviceToHost));
         }
         wbase = wend;
+    }
+    if (xdrop && set == 0) {
+        unsigned int redone = 0;
+        HIPCHK(hipMemcpy(&redone, d_cur + 12, sizeof(redone), hipMemcpyDeviceToHost));
+        g_last_xstats[0] = slots; g_last_xstats[1] = nslices; g_last_xstats[2] = redone; g_last_xstats[3] = (int64_t)store_words;
     }
     c->rx_slots[set] = slots; c->rx_total[set] = (int64_t)wbase; c->rx_on_host[set] = nslices > 1;
     if (total_words) *total_words = (int64_t)wbase;
@@ -558,17 +560,11 @@ int ref_extend_fetch(mhip_ctx* c, int set, mhip_ref_result* res, uint64_t* word_
     return 0;
 }
 
-extern "C" {
+namespace {
 
-int mhip_ref_extend_run_dev(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, int maxc, int tech,
-                            const mhip_ref_candidate* d_cands, const int32_t* d_counts, int64_t* total_words) {
-    HIPCHK(hipSetDevice(c->device));
-    return ref_extend_run(c, ref, reads, rid_begin, rid_end, maxc, tech, d_cands, d_counts, total_words, 0);
-}
-
-int mhip_ref_extend_run(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, int maxc, int tech,
-                        const mhip_ref_candidate* cands, const int32_t* counts, int64_t* total_words) {
-    HIPCHK(hipSetDevice(c->device));
+// a run on HOST lists: the lists go to the device, then ref_extend_run
+int rx_run_host(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, int maxc, int aligner,
+                const mhip_ref_candidate* cands, const int32_t* counts, int64_t* total_words) {
     const int n = rid_end - rid_begin;
     mhip_ref_candidate* d_c = nullptr;
     int32_t* d_n = nullptr;
@@ -579,7 +575,49 @@ int mhip_ref_extend_run(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* 
         HIPCHK(hipMemcpyAsync(d_n, counts, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));       // (the caller's arrays are read until here)
     }
-    return ref_extend_run(c, ref, reads, rid_begin, rid_end, maxc, tech, d_c, d_n, total_words, 0);
+    return ref_extend_run(c, ref, reads, rid_begin, rid_end, maxc, aligner, d_c, d_n, total_words, 0);
+}
+
+// the PacBio entry points keep refusing the other technology: nanopore mode has entry points of its own
+int rx_refuse_tech(mhip_ctx* c, int tech) {
+    if (tech == 0) return 0;
+    c->rx_slots[0] = 0; c->rx_total[0] = 0; c->rx_on_host[0] = false;
+    mhip_set_error("mhip_ref_extend_run: tech = %d: this call is PacBio mode (tech 0, DiffAligner); nanopore mode is mhip_ref_xextend_run", tech);
+    return -1;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mhip_ref_extend_run_dev(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, int maxc, int tech,
+                            const mhip_ref_candidate* d_cands, const int32_t* d_counts, int64_t* total_words) {
+    HIPCHK(hipSetDevice(c->device));
+    if (rx_refuse_tech(c, tech)) return -1;
+    return ref_extend_run(c, ref, reads, rid_begin, rid_end, maxc, RX_ALIGNER_DIFF, d_cands, d_counts, total_words, 0);
+}
+
+int mhip_ref_extend_run(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, int maxc, int tech,
+                        const mhip_ref_candidate* cands, const int32_t* counts, int64_t* total_words) {
+    HIPCHK(hipSetDevice(c->device));
+    if (rx_refuse_tech(c, tech)) return -1;
+    return rx_run_host(c, ref, reads, rid_begin, rid_end, maxc, RX_ALIGNER_DIFF, cands, counts, total_words);
+}
+
+int mhip_ref_xextend_run_dev(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, int maxc,
+                             const mhip_ref_candidate* d_cands, const int32_t* d_counts, int64_t* total_words) {
+    HIPCHK(hipSetDevice(c->device));
+    return ref_extend_run(c, ref, reads, rid_begin, rid_end, maxc, RX_ALIGNER_XDROP, d_cands, d_counts, total_words, 0);
+}
+
+int mhip_ref_xextend_run(mhip_ctx* c, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, int maxc,
+                         const mhip_ref_candidate* cands, const int32_t* counts, int64_t* total_words) {
+    HIPCHK(hipSetDevice(c->device));
+    return rx_run_host(c, ref, reads, rid_begin, rid_end, maxc, RX_ALIGNER_XDROP, cands, counts, total_words);
+}
+
+void mhip_ref_xextend_stats(int64_t out[4]) {
+    for (int i = 0; i < 4; ++i) out[i] = g_last_xstats[i];
 }
 
 int mhip_ref_extend_fetch(mhip_ctx* c, mhip_ref_result* res, uint64_t* word_offs, uint32_t* ops_dense) {

@@ -1,4 +1,5 @@
-// ref_rescue.hip — mecat2ref's clipped-alignment rescue and its result order on the device (stage 3).  PacBio mode.
+// ref_rescue.hip — mecat2ref's clipped-alignment rescue and its result order on the device (stage 3).  Both technologies:
+// only the extension behind the rescue candidates differs (mhip_ref_rescue_run: DiffAligner, mhip_ref_xrescue_run: XdropAligner).
 //
 // Replaces what reference_mapping does with a read's results between its extension loop and the result file
 // (mecat2ref/mecat2ref_impl_large.cpp:584-603 for round 1, :847-866 for round 2):
@@ -178,8 +179,13 @@ __global__ __launch_bounds__(RR_BLOCK) void ref_rescue_finish(const mhip_ref_res
     for (; w < 3 * num_output; ++w) o[w] = -1;
 }
 
-int rr_check(const char* who, const mhip_ref_rescue_params* p, int n) {
-    if (p->tech != 0) { mhip_set_error("%s: technology %d: only PacBio mode (0) is built", who, p->tech); return -1; }
+// tech: the technology of the entry point (0: the PacBio calls, 1: mhip_ref_xrescue_run*); params.tech must name the same one
+int rr_check(const char* who, const mhip_ref_rescue_params* p, int n, int tech = 0) {
+    if (p->tech != tech) {
+        mhip_set_error("%s: technology %d: this call is %s mode (%d); %s", who, p->tech, tech ? "nanopore" : "PacBio", tech,
+                       tech ? "PacBio mode is mhip_ref_rescue_run" : "nanopore mode is mhip_ref_xrescue_run");
+        return -1;
+    }
     if (p->maxc < 1 || p->maxc > RR_MAXC) { mhip_set_error("%s: list length %d outside 1..%d (the order of equal lengths beyond 16 entries is not reproduced)", who, p->maxc, RR_MAXC); return -1; }
     if (p->num_output < 1) { mhip_set_error("%s: num_output %d below 1", who, p->num_output); return -1; }
     if (p->round != 0 && p->round != 1) { mhip_set_error("%s: round %d (0: first, 1: second)", who, p->round); return -1; }
@@ -313,7 +319,7 @@ int64_t g_rescue_stats[4] = {0, 0, 0, 0};
 
 // the stage for reads [rid_begin, rid_end) on DEVICE results d_res [n][maxc]
 int rescue_run(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, const mhip_ref_rescue_params* p,
-               const mhip_ref_result* d_res, int64_t* total_words) {
+               const mhip_ref_result* d_res, int64_t* total_words, int aligner) {
     const int n = rid_end - rid_begin;
     c->rr_n = 0;
     g_rescue_stats[0] = n; g_rescue_stats[1] = g_rescue_stats[2] = g_rescue_stats[3] = 0;
@@ -377,7 +383,7 @@ int rescue_run(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref, const
         g_rescue_stats[2] += cnt[(size_t)i];
     }
     // the rescue candidates through the extension, into the second buffer set: the first extension's results stay where they are
-    if (ref_extend_run(c, ref, reads, rid_begin, rid_end, RR_TRIES, 0, d_cands, d_rcount, total_words, 1)) return -1;
+    if (ref_extend_run(c, ref, reads, rid_begin, rid_end, RR_TRIES, aligner, d_cands, d_rcount, total_words, 1)) return -1;
     mhip_ref_result* d_rres;
     if (scratch_set(c, "rx_res", 1, 0, (void**)&d_rres)) return -1;
     LAUNCH(c, "ref_rescue_finish", ref_rescue_finish, (n + RR_BLOCK - 1) / RR_BLOCK, RR_BLOCK, 0, d_res, (const mhip_ref_rescue_state*)d_st, (const int32_t*)d_rcount,
@@ -388,9 +394,10 @@ int rescue_run(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref, const
     return 0;
 }
 
-int rr_check_run(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, const mhip_ref_rescue_params* p) {
+int rr_check_run(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end, const mhip_ref_rescue_params* p,
+                 int tech = 0) {
     if (rid_begin < 0 || rid_end > reads->num_reads || rid_begin > rid_end) { mhip_set_error("mhip_ref_rescue_run: bad read range [%d,%d)", rid_begin, rid_end); return -1; }
-    if (rr_check("mhip_ref_rescue_run", p, rid_end - rid_begin)) return -1;
+    if (rr_check(tech ? "mhip_ref_xrescue_run" : "mhip_ref_rescue_run", p, rid_end - rid_begin, tech)) return -1;
     if (idx->max_bucket != MAX_BUCKET) { mhip_set_error("mhip_ref_rescue_run needs an index built with mhip_index_build (bucket cap 128), not %d", idx->max_bucket); return -1; }
     if (idx->num_bases != ref->num_bases) { mhip_set_error("mhip_ref_rescue_run: the index was not built from this reference volume"); return -1; }
     for (int r = rid_begin; r < rid_end; ++r)
@@ -399,6 +406,38 @@ int rr_check_run(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref, con
             return -1;
         }
     return 0;
+}
+
+// the two run entry points of technology `tech` (0: DiffAligner behind the rescue candidates, 1: XdropAligner)
+int rr_run_dev(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end,
+               const mhip_ref_rescue_params* p, const mhip_ref_result* d_res, int64_t* total_words, int tech) {
+    HIPCHK(hipSetDevice(c->device));
+    c->rr_n = 0;
+    if (rr_check_run(c, idx, ref, reads, rid_begin, rid_end, p, tech)) return -1;
+    const int n = rid_end - rid_begin;
+    if (!d_res && n > 0) {
+        if (c->rx_slots[0] != n * p->maxc) {
+            mhip_set_error("mhip_ref_rescue_run_dev: the last mhip_ref_extend_run on this context left %d slots, not %d reads x %d", c->rx_slots[0], n, p->maxc);
+            return -1;
+        }
+        if (scratch_set(c, "rx_res", 0, 0, (void**)&d_res)) return -1;
+    }
+    return rescue_run(c, idx, ref, reads, rid_begin, rid_end, p, d_res, total_words, tech ? RX_ALIGNER_XDROP : RX_ALIGNER_DIFF);
+}
+
+int rr_run_host(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end,
+                const mhip_ref_rescue_params* p, const mhip_ref_result* res, int64_t* total_words, int tech) {
+    HIPCHK(hipSetDevice(c->device));
+    c->rr_n = 0;
+    if (rr_check_run(c, idx, ref, reads, rid_begin, rid_end, p, tech)) return -1;
+    const int n = rid_end - rid_begin;
+    mhip_ref_result* d_res = nullptr;
+    if (n > 0) {
+        if (c->scratch("rr_res", sizeof(mhip_ref_result) * (size_t)n * p->maxc, (void**)&d_res)) return -1;
+        HIPCHK(hipMemcpyAsync(d_res, res, sizeof(mhip_ref_result) * (size_t)n * p->maxc, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));       // (the caller's array is read until here)
+    }
+    return rescue_run(c, idx, ref, reads, rid_begin, rid_end, p, d_res, total_words, tech ? RX_ALIGNER_XDROP : RX_ALIGNER_DIFF);
 }
 
 }  // namespace
@@ -415,33 +454,23 @@ void mhip_ref_rescue_params_default(mhip_ref_rescue_params* p, int tech) {
 
 int mhip_ref_rescue_run_dev(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end,
                             const mhip_ref_rescue_params* p, const mhip_ref_result* d_res, int64_t* total_words) {
-    HIPCHK(hipSetDevice(c->device));
-    c->rr_n = 0;
-    if (rr_check_run(c, idx, ref, reads, rid_begin, rid_end, p)) return -1;
-    const int n = rid_end - rid_begin;
-    if (!d_res && n > 0) {
-        if (c->rx_slots[0] != n * p->maxc) {
-            mhip_set_error("mhip_ref_rescue_run_dev: the last mhip_ref_extend_run on this context left %d slots, not %d reads x %d", c->rx_slots[0], n, p->maxc);
-            return -1;
-        }
-        if (scratch_set(c, "rx_res", 0, 0, (void**)&d_res)) return -1;
-    }
-    return rescue_run(c, idx, ref, reads, rid_begin, rid_end, p, d_res, total_words);
+    return rr_run_dev(c, idx, ref, reads, rid_begin, rid_end, p, d_res, total_words, 0);
 }
 
 int mhip_ref_rescue_run(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end,
                         const mhip_ref_rescue_params* p, const mhip_ref_result* res, int64_t* total_words) {
-    HIPCHK(hipSetDevice(c->device));
-    c->rr_n = 0;
-    if (rr_check_run(c, idx, ref, reads, rid_begin, rid_end, p)) return -1;
-    const int n = rid_end - rid_begin;
-    mhip_ref_result* d_res = nullptr;
-    if (n > 0) {
-        if (c->scratch("rr_res", sizeof(mhip_ref_result) * (size_t)n * p->maxc, (void**)&d_res)) return -1;
-        HIPCHK(hipMemcpyAsync(d_res, res, sizeof(mhip_ref_result) * (size_t)n * p->maxc, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));       // (the caller's array is read until here)
-    }
-    return rescue_run(c, idx, ref, reads, rid_begin, rid_end, p, d_res, total_words);
+    return rr_run_host(c, idx, ref, reads, rid_begin, rid_end, p, res, total_words, 0);
+}
+
+/* nanopore mode: the same stage with the X-drop extension (ref_xextend.hip) behind the rescue candidates */
+int mhip_ref_xrescue_run_dev(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end,
+                             const mhip_ref_rescue_params* p, const mhip_ref_result* d_res, int64_t* total_words) {
+    return rr_run_dev(c, idx, ref, reads, rid_begin, rid_end, p, d_res, total_words, 1);
+}
+
+int mhip_ref_xrescue_run(mhip_ctx* c, const mhip_index* idx, const mhip_volume* ref, const mhip_volume* reads, int rid_begin, int rid_end,
+                         const mhip_ref_rescue_params* p, const mhip_ref_result* res, int64_t* total_words) {
+    return rr_run_host(c, idx, ref, reads, rid_begin, rid_end, p, res, total_words, 1);
 }
 
 int mhip_ref_rescue_fetch(mhip_ctx* c, int32_t* out_slots, int32_t* out_counts, mhip_ref_candidate* rescue_cands, int32_t* rescue_counts,

@@ -20,7 +20,8 @@
 // group of eight rows: group g of a wave's scratch = 64 dwords, lane l's dword = the cells rs[a] + l of rows 8 g .. 8 g + 7 — one
 // coalesced 256-byte store per eight rows instead of a 64-byte store per row.  Cells 64.. of the rows that have them (one row in ten)
 // go the same way into a second array of groups behind the first; a bit per group says whether it was written.
-// A block whose window outgrows the ring ends with overflow = 2: the caller redoes it with xdrop_block_wide.  Included by xalign.hip.
+// A block whose window outgrows the ring ends with overflow = 2: the caller redoes it with xdrop_block_wide.  Included by xalign.hip and, with
+// a view and a column sink of its own (xd_defs.h: XNoSink), by ref_xextend.hip.
 #pragma once
 #include <type_traits>
 
@@ -42,7 +43,9 @@ struct XrLds {
 };
 static_assert((((X_MAXN & ~15) - 16) >> 3) + 3 < XR_GROUPS, "the traceback's first window stays inside the wave's group arrays");
 
-__device__ void xdrop_block_ring(XrLds& S, const XView& q, int qidx, int M, const XView& t, int tidx, int N, uint8_t* __restrict__ st, XBlockOut& o) {
+template <class View = XView, class Sink = XNoSink>
+__device__ void xdrop_block_ring(XrLds& S, const View& q, int qidx, int M, const View& t, int tidx, int N, uint8_t* __restrict__ st, XBlockOut& o,
+                                 const Sink& sink = Sink()) {
     xblock_clear(o);
     if (M <= 0 || N <= 0) return;
     const int lane = lane_id();
@@ -320,7 +323,7 @@ __device__ void xdrop_block_ring(XrLds& S, const XView& q, int qidx, int M, cons
         int op = ext ? st_op : own;
         int r = 1, cq = 1, ct = 1;                       // steps of this turn; what the (single) step takes when it is not a run
         uint32_t Mm = (uint32_t)nib0 & 1u;                 // match bits of the turn's substitution steps
-        if (op != 0) { cq = op != XN_GA; ct = op != XN_GB; Mm = 0u; }
+        if (op != 0) { cq = op != XN_GA; ct = op != XN_GB; Mm = 0u; sink.gap(T.n, cq ? 2 : 1); }
         else if (sm & 1u) {                              // (else: a substitution at a cell of row or column 0, alone)
             r = sm == 0xffffffffu ? 32 : __builtin_ctz(~sm);
             Mm = mm & (r >= 32 ? 0xffffffffu : ((1u << r) - 1u));
@@ -341,6 +344,7 @@ __device__ void xdrop_block_ring(XrLds& S, const XView& q, int qidx, int M, cons
             const int gq = op != XN_GA, gt = op != XN_GB;
             a_index -= gq;
             b_index -= gt;
+            sink.gap(T.n, gq ? 2 : 1);
             if (LEAN) ++T.n;
             else T.gap_after_run(gq, gt);
         }

@@ -2,7 +2,8 @@
 // whose window outgrows the ring (low-complexity sequence keeps hundreds of cells within X of the best score).  Scores indexed by b,
 // one script BYTE per cell in rows of XW_WSTRIDE bytes (any window fits), every row's first column in rstart[], and a traceback that
 // reads byte by byte through an LDS window over the rows.  Slower per row than the ring and rare; also the ring's cross-check
-// (MECAT_XD_WIDE=1 runs every block of every unit through it).  Included by xalign.hip.
+// (MECAT_XD_WIDE=1 runs every block of every unit through it).  Included by xalign.hip and, with
+// a view and a column sink of its own (xd_defs.h: XNoSink), by ref_xextend.hip.
 #pragma once
 #include "xd_defs.h"
 
@@ -15,8 +16,9 @@ struct XwWide {
 static_assert(sizeof(XwWide) <= XW_INPLACE_STATE, "the in-place wide state holds one XwWide");
 
 // S: the wave's state, in LDS (xd_extend_w<true>) or in global memory (a ring wave's in-place redo); st: its XW_WIDE_BYTES of script rows
-__device__ inline void xdrop_block_wide(XwWide& S, const XView& q, int qidx, int M, const XView& t, int tidx, int N, uint8_t* __restrict__ st,
-                                 XBlockOut& o) {
+template <class View = XView, class Sink = XNoSink>
+__device__ inline void xdrop_block_wide(XwWide& S, const View& q, int qidx, int M, const View& t, int tidx, int N, uint8_t* __restrict__ st,
+                                        XBlockOut& o, const Sink& sink = Sink()) {
     auto slot = [&](int b) -> int { return min(b, XW_WIDE_HF - 1); };      // (idle lanes read a valid slot)
     auto ldHF = [&](int b, bool in) -> int2 {
         int2 v = S.HF[slot(b)];
@@ -161,6 +163,7 @@ __device__ inline void xdrop_block_wide(XwWide& S, const XView& q, int qidx, int
         const int cm = cq & ct & (byte >> 7);
         a_index -= cq;
         b_index -= ct;
+        if (!(cq & ct)) sink.gap(T.n, cq ? 2 : 1);
         T.step(cq, ct, cm, a_index, b_index);
         if (cq) {
             crs = nrs;

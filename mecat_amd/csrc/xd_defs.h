@@ -26,6 +26,15 @@ __device__ __forceinline__ int xv_at(const XView& v, int i) {
     return (int)(v.comp ? 3u - c : c);
 }
 
+// A block's two template parameters.  The sequence view: any type V with xv_at(const V&, int) -> code of logical base i (XView below is
+// mecat2pw's: a read of a volume, whole-read complement).  The column sink: told every gap column the traceback meets, as
+// gap(i, code) with i = the column's place counted from the block's TAIL (the walk's order, 0 = the last column of the block's
+// strings) and code 1 = target base only, 2 = query base only; wave-uniform.  Substitution columns are not reported: their number
+// follows from XBlockOut::n.  XNoSink keeps nothing (mecat2pw needs counts only).
+struct XNoSink {
+    __device__ __forceinline__ void gap(int, int) const {}
+};
+
 struct XBlockOut {
     int ae, be;                 // aln_qe, aln_te
     int n, nmatch;              // alignment columns / equal columns of the block

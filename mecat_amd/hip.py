@@ -440,6 +440,42 @@ def ref_extend(ctx, ref, reads, rid_begin, rid_end, maxc, cands, counts, tech=0)
     return ref_extend_fetch(ctx, max(rid_end - rid_begin, 0), maxc, tot)
 
 
+_REF_XEXT_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+
+
+def ref_xextend_run(ctx, ref, reads, rid_begin, rid_end, maxc, cands, counts):
+    """mhip_ref_xextend_run: the extension in nanopore mode (XdropAligner) of host lists -> total words; ref_extend_fetch fetches"""
+    cands = np.ascontiguousarray(cands, dtype=REF_CAND_DTYPE)
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    assert cands.size == max(rid_end - rid_begin, 0) * maxc and len(counts) == max(rid_end - rid_begin, 0)
+    tot = C.c_int64()
+    lib().mhip_ref_xextend_run.argtypes = _REF_XEXT_ARGS
+    _chk(lib().mhip_ref_xextend_run(ctx.h, ref.h, reads.h, rid_begin, rid_end, maxc, cands.ctypes.data, counts.ctypes.data, C.byref(tot)))
+    return tot.value
+
+
+def ref_xextend_run_dev(ctx, ref, reads, rid_begin, rid_end, maxc, d_cands, d_counts):
+    """mhip_ref_xextend_run_dev: the same on device lists (mhip_ref_seed_reads_dev's output) -> total words"""
+    tot = C.c_int64()
+    lib().mhip_ref_xextend_run_dev.argtypes = _REF_XEXT_ARGS
+    _chk(lib().mhip_ref_xextend_run_dev(ctx.h, ref.h, reads.h, rid_begin, rid_end, maxc, d_cands, d_counts, C.byref(tot)))
+    return tot.value
+
+
+def ref_xextend(ctx, ref, reads, rid_begin, rid_end, maxc, cands, counts):
+    """run + fetch -> (res, word_offs, words)"""
+    tot = ref_xextend_run(ctx, ref, reads, rid_begin, rid_end, maxc, cands, counts)
+    return ref_extend_fetch(ctx, max(rid_end - rid_begin, 0), maxc, tot)
+
+
+def ref_xextend_stats():
+    """mhip_ref_xextend_stats of the last run: dict(slots, slices, redone (blocks redone with the wide block), store_words)"""
+    v = (C.c_int64 * 4)()
+    lib().mhip_ref_xextend_stats.restype = None
+    lib().mhip_ref_xextend_stats(v)
+    return dict(slots=int(v[0]), slices=int(v[1]), redone=int(v[2]), store_words=int(v[3]))
+
+
 def ref_extend_stats():
     """mhip_ref_extend_stats of the last run: dict(slots, slices, row_bytes, store_words)"""
     v = (C.c_int64 * 4)()
@@ -488,6 +524,25 @@ def ref_rescue_run_dev(ctx, idx, ref, reads, rid_begin, rid_end, params, d_res=N
     tot = C.c_int64()
     lib().mhip_ref_rescue_run_dev.argtypes = _REF_RESCUE_ARGS
     _chk(lib().mhip_ref_rescue_run_dev(ctx.h, idx.h, ref.h, reads.h, rid_begin, rid_end, C.byref(params), d_res, C.byref(tot)))
+    return tot.value
+
+
+def ref_xrescue_run(ctx, idx, ref, reads, rid_begin, rid_end, params, res):
+    """mhip_ref_xrescue_run: the rescue stage in nanopore mode (params.tech must be 1) on host results -> total words; ref_rescue_fetch
+    fetches"""
+    res = np.ascontiguousarray(res, dtype=REF_RESULT_DTYPE)
+    assert res.shape == (max(rid_end - rid_begin, 0), params.maxc)
+    tot = C.c_int64()
+    lib().mhip_ref_xrescue_run.argtypes = _REF_RESCUE_ARGS
+    _chk(lib().mhip_ref_xrescue_run(ctx.h, idx.h, ref.h, reads.h, rid_begin, rid_end, C.byref(params), res.ctypes.data, C.byref(tot)))
+    return tot.value
+
+
+def ref_xrescue_run_dev(ctx, idx, ref, reads, rid_begin, rid_end, params, d_res=None):
+    """mhip_ref_xrescue_run_dev: the same on device results; None = those of the last ref_xextend_run* on this context"""
+    tot = C.c_int64()
+    lib().mhip_ref_xrescue_run_dev.argtypes = _REF_RESCUE_ARGS
+    _chk(lib().mhip_ref_xrescue_run_dev(ctx.h, idx.h, ref.h, reads.h, rid_begin, rid_end, C.byref(params), d_res, C.byref(tot)))
     return tot.value
 
 
