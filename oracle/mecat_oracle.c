@@ -926,6 +926,7 @@ struct orc_xaligner {                                         /* xdrop_gapalign.
     int matrix[4][4];
     char *lq, *lt, *rq, *rt, *tq, *tt;                         /* left/right/tmp aligned strings (codes 0..4) */
     int lsize, rsize;
+    int *trace_fb, *trace_bs, trace_rows;                      /* orc_xdrop_align_trace: the rows' windows, where set (not the reference's) */
 };
 
 orc_xaligner* orc_xaligner_new(void)
@@ -995,8 +996,11 @@ static int xdrop_align(orc_xaligner* X, const char* A, int M, const char* B, int
     b_size = i;
     best_score = 0;
     first_b_index = 0;
+    X->trace_rows = 0;
     for (a_index = 1; a_index <= M; ++a_index) {
         const uint8_t AC = (uint8_t)extract_char(A, a_index - 1, forward);
+        if (X->trace_fb) { X->trace_fb[a_index - 1] = first_b_index; X->trace_bs[a_index - 1] = b_size; }
+        X->trace_rows = a_index;
         edit_script[a_index] = state_array + states_used + 1;
         edit_start_offset[a_index] = first_b_index;
         edit_script_row = edit_script[a_index] - first_b_index;
@@ -1049,6 +1053,7 @@ static int xdrop_align(orc_xaligner* X, const char* A, int M, const char* B, int
             ++b_size;
         }
     }
+    if (X->trace_fb) { X->trace_fb[X->trace_rows] = first_b_index; X->trace_bs[X->trace_rows] = b_size; }
     a_index = *ae;
     b_index = *be;
     script = X_SUB;
@@ -1084,6 +1089,15 @@ int orc_xdrop_align(orc_xaligner* a, const char* A, int M, const char* B, int N,
     res[0] = ae; res[1] = be; res[2] = a->num_ops;
     for (int i = 0; i < a->num_ops; ++i) { ops[2 * i] = a->op_type[i]; ops[2 * i + 1] = a->op_num[i]; }
     return sc;
+}
+
+int orc_xdrop_align_trace(orc_xaligner* a, const char* A, int M, const char* B, int N, int forward, int* res, int* ops, int* fb, int* bs)
+{
+    a->trace_fb = fb; a->trace_bs = bs; a->trace_rows = 0;
+    if (fb) { fb[0] = 0; bs[0] = 0; }                          /* M <= 0 or N <= 0: no row, an empty window behind it */
+    orc_xdrop_align(a, A, M, B, N, forward, res, ops);
+    a->trace_fb = NULL; a->trace_bs = NULL;
+    return a->trace_rows;
 }
 
 /* script_to_aligned_string, xdrop_gapalign.cpp:215-261 ; returns the string length */

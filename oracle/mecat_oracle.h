@@ -155,6 +155,11 @@ void orc_xaligner_free(orc_xaligner* a);
    last element like align_ex does); returns the best score; res = {ae, be, num_ops}; ops receives num_ops pairs
    (op_type, count) in edit_block order (i.e. from the alignment end towards its start) */
 int orc_xdrop_align(orc_xaligner* a, const char* A, int M, const char* B, int N, int forward, int* res, int* ops);
+/* the same call (the one xdrop_align body, which fills the two arrays while they are set) with the window of every row that was entered:
+   fb[a - 1], bs[a - 1] = first_b_index, b_size at the entry of row a = 1, 2, ...; one more entry behind the last row entered holds the two
+   values as that row left them (what row a + 1 would have been entered with).  Returns the number of rows entered (<= M); fb and bs
+   hold M + 1 ints each */
+int orc_xdrop_align_trace(orc_xaligner* a, const char* A, int M, const char* B, int N, int forward, int* res, int* ops, int* fb, int* bs);
 int orc_xdrop_go(orc_xaligner* a, const char* query, int qstart, int qsize, const char* target, int tstart, int tsize,
                  int min_aln_size, orc_aln_result* out);     /* xdrop_gapalign.cpp:359-439 */
 

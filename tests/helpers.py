@@ -161,6 +161,7 @@ def orc():
         L.orc_xaligner_new.restype = vp
         L.orc_xaligner_free.argtypes = [vp]
         L.orc_xdrop_align.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
+        L.orc_xdrop_align_trace.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp]
         L.orc_xdrop_go.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(OrcAlnResult)]
         L.orc_map_read_x.argtypes = [C.POINTER(OrcVolume), C.POINTER(OrcVolume), C.POINTER(OrcIndex), vp, vp, vp, C.c_int,
                                      C.POINTER(OrcParams), vp]
